@@ -7,8 +7,12 @@ configs[1]); utterances are sharded across GPUs (weak scaling, one process per G
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the task contract): metric = audio-sec/s with inputs resident in HBM, plus
+Prints ONE JSON line on rank 0 (see the task contract): metric = audio-sec/s with inputs resident in HBM.  A plain run sets
+up, warms up, times ``--steps`` steps of the headline mode (two batches per forward; one batch at a time with
+``--in-flight 1``), writes that mode's last step with ``--dump-outputs DIR`` and prints the line.  ``--full`` times every
+leg and adds
 
+* the other throughput modes, of which the faster one gives ``value``, and the one-batch leg in both stack schedules;
 * ``roofline`` for the dominant kernel (the persistent LSTM recurrence): ``achieved`` / ``frac`` = SURVEY 8d's ALGORITHMIC
   bytes per launch / the launch duration measured live with HIP events on the launch stream / 8 TB/s (the north-star's
   definition; it re-reads ``W_hh`` every step although the kernel keeps it in registers, so it can exceed 1 and says
@@ -28,6 +32,7 @@ import json
 import os
 import subprocess
 import sys
+import threading
 import time
 
 import numpy as np
@@ -221,7 +226,7 @@ def f32_child(args):
     """The fp32-arithmetic figure, timed by the driver's own run: a child process in MS_PRECISION=f32 (the mode is read
     once per process), started BEFORE this process makes its first GPU call, run to completion, its JSON line kept."""
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(max(10, args.steps // 2)), "--warmup",
-           str(args.warmup), "--precision", "f32", "--no-cpu-baseline", "--no-f32-child", "--no-frontend", "--no-legs", "--detail-path", os.devnull]
+           str(args.warmup), "--full", "--precision", "f32", "--no-cpu-baseline", "--no-f32-child", "--no-frontend", "--no-legs", "--detail-path", os.devnull]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -263,7 +268,7 @@ def gather_one_rank_child(args):
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(max(10, args.steps // 2)), "--warmup",
-           str(args.warmup), "--gather-logits", "--no-cpu-baseline", "--no-f32-child", "--no-frontend", "--no-legs", "--no-ragged",
+           str(args.warmup), "--full", "--gather-logits", "--no-cpu-baseline", "--no-f32-child", "--no-frontend", "--no-legs", "--no-ragged",
            "--reps", "0", "--detail-path", os.devnull]
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                MS_FORCE_COLLECTIVE="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
@@ -327,6 +332,64 @@ def bench_line(full, detail_name):
     raise RuntimeError(f"the standard keys alone exceed {LINE_LIMIT} bytes")
 
 
+def headline_record(world, args, elapsed, mode, latency_ms):
+    """The line's standard keys and the headline's `config`, the same in a plain and a --full run.  `mode` names the runner
+    that was timed for `value`: two_batches_per_forward, two_batches_in_flight or one_batch_in_flight."""
+    return {
+        "metric": "audio-sec/s (RTF), DS2 5xBiLSTM-1024 encoder forward + CTC greedy, 80-feature 10 s clips @ batch 32/GPU",
+        "value": round(world * BATCH_PER_GPU * CLIP_SECONDS * args.steps / elapsed, 1), "unit": "audio-sec/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": precision_label(), "data": "synthetic",
+        "config": {"workload": "configs[1]: DS2 2xconv2d + 5xBiLSTM-1024 + FC, 80 feat x 1001 frames (10 s), batch 32/GPU, CTC greedy",
+                   "global_batch": world * BATCH_PER_GPU, "frames": FRAMES, "parallelism": f"utterance-shard x{world}",
+                   "in_flight": 1 if mode == "one_batch_in_flight" else 2,
+                   "pipeline": ("two batches per forward (myrtlespeech_amd.pipeline.PairedBatches): consecutive batches of 32 go "
+                                "through the network two at a time on one stream; the two batches' recurrences run side by side "
+                                "in one launch of the wide-workgroup kernel, every other kernel once on 64 utterances; every "
+                                "step's full work incl. decode completes inside the timed region; outputs bit-identical to "
+                                "the one-batch path") if mode == "two_batches_per_forward" else
+                               ("two batches in flight per GPU on two HIP streams (myrtlespeech_amd.pipeline.TwoBatchesInFlight): "
+                                "this batch's wide-workgroup recurrence takes half of the CUs, the next batch's projection GEMMs the rest; "
+                                "every step's full work incl. decode completes inside the timed region; outputs "
+                                "bit-identical to the one-batch path") if mode == "two_batches_in_flight" else "one batch at a time",
+                   "decode": "all-gather logits, batched decode on every rank" if args.gather_logits else
+                             "per-shard decode (no data-path collective)",
+                   # flat scalars (the driver's record keeps scalars of `config`, not nested objects)
+                   "headline_mode": mode,
+                   "headline_latency_ms_per_batch": round(latency_ms, 3)}}
+
+
+def dump_outputs(path, last):
+    """`last` = (logits [T, N, V], their lengths [N], the N greedy transcripts) of the headline mode's last timed step, as its
+    caller receives them -> path/logits.npy (float32), path/logit_lengths.npy and path/transcripts.npy (float64; one row per
+    utterance, padded with -1 to the longest transcript)."""
+    logits, lens, transcripts = last
+    os.makedirs(path, exist_ok=True)
+    tr = np.full((len(transcripts), max([len(t) for t in transcripts], default=0)), -1.0)
+    for i, t in enumerate(transcripts):
+        tr[i, :len(t)] = t
+    np.save(os.path.join(path, "logits.npy"), logits.numpy().astype(np.float32))
+    np.save(os.path.join(path, "logit_lengths.npy"), lens.numpy().astype(np.float64))
+    np.save(os.path.join(path, "transcripts.npy"), tr)
+
+
+def emit_record(out, args, json_fd, last):
+    """Rank 0's output: the full record to --detail-path and stderr, the outputs to --dump-outputs, then the ONE stdout line
+    of numbers under LINE_LIMIT bytes."""
+    full = json.dumps(out, indent=1, default=str)
+    try:
+        with open(args.detail_path, "w") as f:
+            f.write(full + "\n")
+    except OSError as e:
+        sys.stderr.write(f"bench: could not write {args.detail_path}: {e}\n")
+    sys.stderr.write(full + "\n")
+    sys.stderr.flush()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    sys.stdout.flush()
+    os.write(json_fd, (bench_line(out, os.path.basename(args.detail_path)) + "\n").encode())
+
+
 def spawn_ranks(argv, n):
     """`python bench.py --gpus N` without torchrun: start the N ranks as ONE child --
     `python -m torch.distributed.run --nproc-per-node N bench.py ...` -- BEFORE this process makes any GPU call, relay rank 0's
@@ -351,6 +414,14 @@ def main(argv=None, runtime=None, json_fd=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="time every leg, not only the headline mode: the other throughput modes (the faster one gives "
+                         "`value`), the one-batch leg, per-kernel spans and rooflines, repeat regions, ragged lengths, the "
+                         "f32 / fp16 / one-rank children, the waveform front end, CPU baselines and the other BASELINE configs; "
+                         "the --no-* and --reps options below act on this run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline mode computed in its last timed step (rank 0's logits, their lengths and "
+                         "the transcripts) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-f32-child", action="store_true", help="skip the MS_PRECISION=f32 child run")
     ap.add_argument("--no-frontend", action="store_true", help="skip the waveform -> MFCC side measurement")
@@ -361,7 +432,8 @@ def main(argv=None, runtime=None, json_fd=None):
                     help="batches in flight per GPU for the headline figure: 2 (default) = myrtlespeech_amd.pipeline."
                          "TwoBatchesInFlight (two streams, the next batch's projection GEMMs run beside this batch's "
                          "persistent recurrence; bit-identical results, per-batch latency of two batches); 1 = one batch "
-                         "at a time.  The one-batch leg is always timed too (kernel durations / rooflines come from it)")
+                         "at a time.  With --full the one-batch leg is always timed too (kernel durations / rooflines come "
+                         "from it)")
     ap.add_argument("--precision", choices=["f16x3", "bf16x3", "f32", "fp16"], default=None,
                     help="operand mode of the recurrence / projection kernels (default: MS_PRECISION or f16x3); "
                          "f32 = float32 MFMA everywhere")
@@ -401,10 +473,10 @@ def main(argv=None, runtime=None, json_fd=None):
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
 
     f32 = stream_fp16 = None
-    if world == 1 and "RANK" not in os.environ and precision_mode() == "f16x3" and not args.no_f32_child:
+    if args.full and world == 1 and "RANK" not in os.environ and precision_mode() == "f16x3" and not args.no_f32_child:
         f32 = f32_child(args)          # before the first GPU call of this process
     gather1 = None
-    if world == 1 and "RANK" not in os.environ and precision_mode() == "f16x3" and not args.no_legs:
+    if args.full and world == 1 and "RANK" not in os.environ and precision_mode() == "f16x3" and not args.no_legs:
         stream_fp16 = fp16_stream_child()
         gather1 = gather_one_rank_child(args)
 
@@ -429,6 +501,9 @@ def main(argv=None, runtime=None, json_fd=None):
     x = rt.to_device(torch.randn(n_rank, 1, FEATURES, FRAMES, generator=g))
     lens_full = torch.full((n_rank,), FRAMES, dtype=torch.int64)
     lens_ragged = torch.sort(torch.randint(501, FRAMES + 1, (n_rank,), generator=g), descending=True).values
+    # the logits each issuing thread decoded last and the thread that issued each batch of a runner's call: a thread's batches
+    # are decoded in order, so the issuer of a call's last batch holds that batch's logits when the call returns
+    latest, issuer = {}, {}
 
     def step_launch(lens, ev=None):
         """Enqueue one whole step (encoder forward, greedy decode, copy of the transcripts to pinned host memory) on the
@@ -445,6 +520,7 @@ def main(argv=None, runtime=None, json_fd=None):
         if args.gather_logits and dist is not None:
             from myrtlespeech_amd.parallel import gather_logits
             logits, out_lens = gather_logits(logits, out_lens)
+        latest[threading.get_ident()] = (logits, out_lens)
         pending = decoder.launch(logits, out_lens)
         if ev is not None:
             e2.record()
@@ -485,18 +561,20 @@ def main(argv=None, runtime=None, json_fd=None):
         def pre(k):
             starts[k] = rt.event()
             starts[k].record()
+            issuer[k] = threading.get_ident()
 
         def post(out):
             logits, out_lens = out[0][0], out[0][1]
             if gathering:        # this batch's shard of logits from every rank, then the batched decode on every rank
                 from myrtlespeech_amd.parallel import gather_logits
                 logits, out_lens = gather_logits(logits, out_lens)
+            latest[threading.get_ident()] = (logits, out_lens)
             pending = decoder.launch(logits, out_lens)
             end = rt.event()
             end.record()
             return pending, end
 
-        pipe = None if gathering else rt.pipe(model, post, pre)
+        pipe = None if (gathering or not args.full) else rt.pipe(model, post, pre)
         paired = rt.paired(model, post, pre)
 
     STAGES = ("projection", "recurrence", "gemm_k_large", "gemm_k_small", "conv", "layout", "linear", "greedy", "other")
@@ -519,7 +597,7 @@ def main(argv=None, runtime=None, json_fd=None):
             runner = two if callable(two) else pipe          # `two` = the throughput mode's runner (True: the threaded pipeline)
             pend = runner([(x if lens is lens_full else x_ragged, lens)] * steps)
             for pd, _ in pend:
-                pd.result()                      # every step's transcripts are on the host before the clock stops
+                transcripts = pd.result()        # every step's transcripts are on the host before the clock stops
         else:
             prev = None
             for _ in range(steps):
@@ -529,9 +607,13 @@ def main(argv=None, runtime=None, json_fd=None):
                 elif prev is not None:
                     prev.result()
                 prev = cur
-            prev.result()
+            transcripts = prev.result()
         rt.synchronize()
         elapsed = time.perf_counter() - t0
+        last = None
+        if args.dump_outputs:                    # the last step's outputs, copied to the host outside the timed span
+            logits, out_lens = latest[issuer[steps - 1] if two else threading.get_ident()]
+            last = (logits.detach().float().cpu(), out_lens.detach().cpu(), transcripts)
         barrier()
         lib.ms_prof_read(ms, cnt)
         lib.ms_prof_enable(0)
@@ -539,7 +621,7 @@ def main(argv=None, runtime=None, json_fd=None):
         t_max = torch.tensor([elapsed], dtype=torch.float64, device=rt.device)
         if dist is not None:
             dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
-        r = {"elapsed": float(t_max.item()), "steps": steps,
+        r = {"elapsed": float(t_max.item()), "steps": steps, "last": last,
              "per_launch": {k: ms[i] / max(cnt[i], 1) for i, k in enumerate(STAGES)},
              "per_step": {k: ms[i] / steps for i, k in enumerate(STAGES)},
              "launches_per_step": {k: cnt[i] / steps for i, k in enumerate(STAGES)}}
@@ -572,9 +654,27 @@ def main(argv=None, runtime=None, json_fd=None):
             out["wall_ms_per_step"] = round(r["elapsed"] / r["steps"] * 1e3, 4)
         return out
 
+    def teardown():
+        if dist is not None:
+            parallel.drop_host_groups()
+            dist.destroy_process_group()
+
     x_ragged = x.clone()
     for _ in range(args.warmup):
         step(lens_full)
+    if not args.full:
+        # the headline mode alone, without in-library spans: two batches per forward -- the throughput mode the --full run
+        # finds the faster one on this workload -- or, with --in-flight 1, one batch at a time in the library's default schedule
+        if pipelined:
+            paired([(x, lens_full)] * max(2, args.warmup, min(args.steps, 24)))      # the runner's own warm-up, as in leg 3
+        r = timed(lens_full, args.steps, paired if pipelined else False, prof=False)
+        if rank == 0:
+            out = headline_record(world, args, r["elapsed"], "two_batches_per_forward" if pipelined else "one_batch_in_flight",
+                                  r["latency"] if pipelined else r["span"])
+            out["latency_ms_per_batch"] = out["config"]["headline_latency_ms_per_batch"]
+            emit_record(out, args, json_fd, r["last"])
+        teardown()
+        return
     # leg 1: one batch at a time, LAYER BY LAYER (projection, then recurrence: every kernel alone on the device -- kernel
     # durations, rooflines, the stage table, the encoder / decode split)
     overlap_available = set_overlap(False)
@@ -828,30 +928,11 @@ def main(argv=None, runtime=None, json_fd=None):
             else:
                 gemm["traffic"] = None
                 gemm["pmc_note"] = gwhy
-        out = {
-            "metric": "audio-sec/s (RTF), DS2 5xBiLSTM-1024 encoder forward + CTC greedy, 80-feature 10 s clips @ batch 32/GPU",
-            "value": round(value, 1), "unit": "audio-sec/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": precision_label(), "data": "synthetic",
-            "config": {"workload": "configs[1]: DS2 2xconv2d + 5xBiLSTM-1024 + FC, 80 feat x 1001 frames (10 s), batch 32/GPU, CTC greedy",
-                       "global_batch": world * BATCH_PER_GPU, "frames": FRAMES, "parallelism": f"utterance-shard x{world}",
-                       "in_flight": 2 if pipelined else 1,
-                       "pipeline": ("two batches per forward (myrtlespeech_amd.pipeline.PairedBatches): consecutive batches of 32 go "
-                                    "through the network two at a time on one stream; the two batches' recurrences run side by side "
-                                    "in one launch of the wide-workgroup kernel, every other kernel once on 64 utterances; every "
-                                    "step's full work incl. decode completes inside the timed region; outputs bit-identical to "
-                                    "the one-batch path") if (pipelined and headline is paired) else
-                                   ("two batches in flight per GPU on two HIP streams (myrtlespeech_amd.pipeline.TwoBatchesInFlight): "
-                                    "this batch's wide-workgroup recurrence takes half of the CUs, the next batch's projection GEMMs the rest; "
-                                    "every step's full work incl. decode completes inside the timed region; outputs "
-                                    "bit-identical to the one-batch path") if pipelined else "one batch at a time",
-                       "decode": "all-gather logits, batched decode on every rank" if args.gather_logits else
-                                 "per-shard decode (no data-path collective)",
-                       # flat scalars (the driver's record keeps scalars of `config`, not nested objects): the literal
-                       # "batch 32, one batch at a time" step and the strict-f32 figure beside the headline
-                       "headline_mode": ("two_batches_per_forward" if (pipelined and headline is paired) else
-                                         "two_batches_in_flight" if pipelined else "one_batch_in_flight"),
-                       "headline_latency_ms_per_batch": round(latency_ms if pipelined else one["span"], 3),
+        headline_mode = ("two_batches_per_forward" if (pipelined and headline is paired) else
+                         "two_batches_in_flight" if pipelined else "one_batch_in_flight")
+        out = headline_record(world, args, elapsed, headline_mode, latency_ms if pipelined else one["span"])
+        out["config"].update({
+                       # flat scalars beside the headline: the literal "batch 32, one batch at a time" step, the strict-f32 figure
                        # the one-batch leg is the FIRST thing timed after W warm-up steps and its first region runs 4 .. 12 % slower
                        # than the four that follow (allocator / clock settling): the side figure is the median region, the first
                        # region is kept beside it; `value` (the headline) stays its first region, as the contract says
@@ -871,7 +952,8 @@ def main(argv=None, runtime=None, json_fd=None):
                        "one_batch_ms_per_step_min": spread["one_batch_ms_per_step"]["min"],
                        # the second kernel's figures as scalars too (the nested `projection_gemm` object may be cut from the line)
                        "projection_gemm_launch_ms": gemm.get("launch_ms"), "projection_gemm_frac": gemm.get("frac"),
-                       "recurrence_launch_ms": roof.get("launch_ms")},
+                       "recurrence_launch_ms": roof.get("launch_ms")})
+        out.update({
             "timing": spread,
             "stages": {"one_batch": {k: round(one["per_step"][k], 3) for k in ("conv", "layout", "projection", "recurrence", "linear", "greedy")},
                        "headline": ({k: round((pair if headline is paired else two)["per_step"][k], 3)
@@ -906,7 +988,7 @@ def main(argv=None, runtime=None, json_fd=None):
                        "measured_trained_scale_max_abs_logit_error": 8.8e-4, "measured_default_init_max_abs_logit_error": 7.8e-8},
             "kernel_ms": {"lstm_recurrent_per_layer": round(rec_ms, 3), "lstm_input_projection_per_layer": round(proj_ms, 3)},
             "roofline": roof, "projection_gemm": gemm,
-        }
+        })
         if two_in_flight is not None:
             two_in_flight["what_binds"] = (
                 "each layer slot = one batch's wide-workgroup recurrence on half of the CUs beside the other batch's projection "
@@ -959,20 +1041,10 @@ def main(argv=None, runtime=None, json_fd=None):
             cal = detail.get("calibration") or {}
             for k_, v_ in cal.items():
                 out["config"]["calib_" + k_] = v_
-        # the full record: a side file + stderr; stdout gets ONE line of numbers under LINE_LIMIT bytes
-        full = json.dumps(out, indent=1, default=str)
-        try:
-            with open(args.detail_path, "w") as f:
-                f.write(full + "\n")
-        except OSError as e:
-            sys.stderr.write(f"bench: could not write {args.detail_path}: {e}\n")
-        sys.stderr.write(full + "\n")
-        sys.stderr.flush()
-        sys.stdout.flush()
-        os.write(json_fd, (bench_line(out, os.path.basename(args.detail_path)) + "\n").encode())
-    if dist is not None:
-        parallel.drop_host_groups()
-        dist.destroy_process_group()
+        leg = ((pair if headline_mode == "two_batches_per_forward" else two) if pipelined else
+               (one_ov if one_ov is not None else one))
+        emit_record(out, args, json_fd, leg["last"])
+    teardown()
 
 
 if __name__ == "__main__":

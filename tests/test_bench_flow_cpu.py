@@ -7,6 +7,7 @@ import os
 import socket
 import time
 
+import numpy as np
 import torch
 import torch.multiprocessing as mp
 
@@ -181,7 +182,7 @@ def _worker(rank, world, port, out_dir, extra):
         json.dump(rt.log, f)
 
 
-def _run(tmp_path, extra):
+def _spawn(tmp_path, extra):
     world = 2
     ctx = mp.get_context("spawn")
     port = _free_port()
@@ -196,7 +197,12 @@ def _run(tmp_path, extra):
     assert (tmp_path / "rank1.json").read_text().strip() == ""        # ONE JSON line, from rank 0
     assert len(lines) == 1
     logs = [json.loads((tmp_path / f"log{r}.json").read_text()) for r in range(world)]
-    line = _check_line(lines[0])
+    return lines[0], logs
+
+
+def _run(tmp_path, extra):
+    text, logs = _spawn(tmp_path, ["--full"] + list(extra))
+    line = _check_line(text)
     assert line["detail"] == "detail.json"
     # the nested per-mode records live in the side file; the line carries the standard keys and numbers
     detail = json.loads((tmp_path / "detail.json").read_text())
@@ -277,6 +283,34 @@ def test_bench_control_flow_two_ranks_gather_logits_unequal_shards(tmp_path):
         assert all(v <= T_RANK[0] for v in full[:N_RANK[0]]) and all(v <= T_RANK[1] for v in full[N_RANK[0]:])
 
 
+def test_plain_run_times_only_the_headline_mode_and_dumps_its_last_step(tmp_path):
+    """Without --full: W warm-up steps, the paired runner's own warm-up, exactly K timed steps of two batches per forward with
+    no in-library spans -- no other leg -- then rank 0's last step as .npy files and the line with the standard keys."""
+    dump = tmp_path / "out"
+    text, logs = _spawn(tmp_path, ["--dump-outputs", str(dump)])
+    line = json.loads(text, parse_constant=_reject_constant)
+    assert len(text.encode()) < 8192 and line["detail"] == "detail.json"
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "audio-sec/s" and line["higher_is_better"] is True and isinstance(line["dtype"], str)
+    assert line["config"]["headline_mode"] == "two_batches_per_forward" and line["config"]["in_flight"] == 2
+    assert all(not isinstance(v, (dict, list)) for v in line["config"].values())
+    assert not {"roofline", "cpu_baseline", "legs", "timing", "stages", "ragged_lengths"} & set(line)
+    for rank, log in enumerate(logs):
+        kinds = [e[0] for e in log]
+        assert "pipe" not in kinds and [e[1] for e in log if e[0] == "paired"] == [3, 3]     # warm-up, then the K timed steps
+        assert ["prof_enable", 1] not in log
+        assert kinds.count("decode") == 1 + 3 + 3                                          # W + warm-up + K
+    logits = np.load(dump / "logits.npy")
+    assert logits.dtype == np.float32 and np.array_equal(logits, _shard_logits(0).numpy())
+    lens = np.load(dump / "logit_lengths.npy")
+    assert lens.dtype == np.float64 and lens.tolist() == [T_RANK[0]] * N_RANK[0]
+    transcripts = np.load(dump / "transcripts.npy")
+    assert transcripts.dtype == np.float64 and transcripts.tolist() == [[1.0, 2.0]] * N_RANK[0]
+    assert sorted(os.listdir(dump)) == ["logit_lengths.npy", "logits.npy", "transcripts.npy"]
+
+
 def test_bench_line_stays_parseable_whatever_the_detail_grows_to():
     """Round 4's own 22.9 KB record (the one the driver could not parse) goes through `bench_line`: under 8 KB, strict JSON,
     `roofline.frac`, `cpu_baseline.value`, `config.workload`, `dtype`, `ms_per_step` and the compact `legs` still there."""
@@ -322,7 +356,7 @@ def test_bench_spawns_its_own_ranks_without_torchrun(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-frontend",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-frontend",
            "--runtime", "tests.test_bench_flow_cpu:_CpuRuntime", "--detail-path", str(tmp_path / "detail.json")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -46,9 +46,10 @@ def test_baton_alternates_round_robin_and_skips_finished_threads():
         assert order == expect
 
 
-def test_pipeline_argument_checks_need_no_gpu():
+def test_pipeline_argument_checks_need_no_gpu(monkeypatch):
     import torch
     from myrtlespeech_amd.pipeline import BatchesInFlight
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)      # no HIP device, on a GPU box too
     with pytest.raises(RuntimeError):          # no HIP device here: there is no CPU fallback
         BatchesInFlight(torch.nn.Identity())
 

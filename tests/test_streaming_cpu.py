@@ -22,7 +22,8 @@ def _torch_conv_forward(x4, seq_lens, weight4, bias, packed, stride, dilation, g
     kf = weight4.shape[2]
     pf = pad_same(x.shape[2], kf, stride[0], dilation[0]) if same else (0, 0)
     x = F.pad(x, (0, 0, pf[0], pf[1]))
-    y = F.conv2d(x, weight4, bias, stride=stride, dilation=dilation, groups=groups)
+    # (the module keeps its weights on the device where there is one; this stand-in computes on the host)
+    y = F.conv2d(x, weight4.cpu(), None if bias is None else bias.cpu(), stride=stride, dilation=dilation, groups=groups)
     if act is not None:
         y = y.clamp(act[0], act[1])
     return y, None
@@ -50,7 +51,7 @@ def test_conv_stream_operators_reproduce_full_length_same_convolutions(monkeypat
     # full length: the oracle's masked SAME convolutions, layer by layer (lens travel like cnn.py:191-197)
     h, hl = x.numpy().copy(), lens.copy()
     for c, (kt, st, dt) in zip(convs, geo):
-        h, hl = O.mask_conv2d(h, hl, c.weight.detach().numpy(), c.bias.detach().numpy(), stride=(1, st), padding_same=True,
+        h, hl = O.mask_conv2d(h, hl, c.weight.detach().cpu().numpy(), c.bias.detach().cpu().numpy(), stride=(1, st), padding_same=True,
                               dilation=(1, dt))
         h = np.clip(h, 0.0, 20.0)
     # streamed, with a chunk size drawn per call

@@ -15,7 +15,7 @@ export MS_RNN_OVERLAP=0
 pass() {
   local name=$1; shift
   echo "[pmc_bench] pass $name: $*"
-  timeout -k 10 240 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-f32-child --no-frontend --no-ragged --no-legs --reps 0 --detail-path /dev/null --in-flight 1 > $OUT.$name.log 2>&1 || { echo "[pmc_bench] pass $name failed or timed out"; tail -5 $OUT.$name.log; return 1; }
+  timeout -k 10 240 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-f32-child --no-frontend --no-ragged --no-legs --reps 0 --detail-path /dev/null --in-flight 1 > $OUT.$name.log 2>&1 || { echo "[pmc_bench] pass $name failed or timed out"; tail -5 $OUT.$name.log; return 1; }
 }
 mkdir -p $OUT
 pass p1 FETCH_SIZE || exit 1
