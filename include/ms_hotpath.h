@@ -389,6 +389,31 @@ int ms_ctc_loss_backward(const float* logits, const int32_t* in_lens, const int3
 int ms_ctc_greedy_decode(const float* x, const int32_t* lens, int32_t* out_idx, int32_t* out_len, int T, int N,
                          int V, int blank, void* stream);
 
+/* The same decode advanced one chunk of logit rows at a time (ctc_greedy_decoder.py:74-92, its frame loop cut between
+ * frames; the reference has no streaming decoder).  Everything a stream carries between two steps -- the symbol of its
+ * last existing row, its label count, its rows seen, one sticky overflow word for the batch -- lives in `state`
+ * (ms_ctc_greedy_stream_state_bytes(N) bytes of device memory; host arithmetic, 0 for N <= 0), as int32 words:
+ * [0] the overflow word, [1 .. 15] reserved, then four per stream i at [16 + 4 i]: previous symbol (-1: none), label
+ * count, frames seen, reserved.  _begin: no previous symbol, 0 labels, 0 frames seen, overflow word cleared.
+ * _step: x [rows, n, V] are the next `rows` logit rows of the first n <= N streams (streams leave a sorted batch as a
+ * suffix).  Any real scores; arg max as ms_ctc_greedy_decode has it: first maximum wins, NaN counts as the maximum,
+ * first NaN wins.  Rows that exist for stream i: chunk_lens[i] (clamped to [0, rows]) if chunk_lens is given,
+ * otherwise clamp(total_lens[i] - frames_seen[i], 0, rows); exactly one of the two is non-NULL.  frames_seen[i]
+ * advances by the rows that existed.  A row's symbol is kept iff it is not `blank` and differs from the symbol of the
+ * stream's previous existing row -- for a chunk's first row the one carried in `state`, none at the start of the clip.
+ * Kept symbols are appended to labels [N, cap] at the stream's running label count; label_frames [N, cap] (may be NULL)
+ * gets the 0-based index, counted over the stream's existing rows since _begin, of the row that emitted the label (where
+ * its run began).  A stream that would exceed `cap` labels stops appending, keeps counting and sets the overflow word.
+ * fresh [N, 1 + rows] (may be NULL): column 0 = labels this call appended for the stream (0 for streams n .. N-1),
+ * columns 1.. = those labels: one small device-to-host copy per step delivers the news.
+ * No host synchronisation, no host-read counter, no allocation: steps with a fixed `rows` can be captured into a HIP
+ * graph on one stream and replayed. */
+size_t ms_ctc_greedy_stream_state_bytes(int N);
+int ms_ctc_greedy_stream_begin(void* state, int N, void* stream);
+int ms_ctc_greedy_stream_step(const float* x, int rows, int n, int V, int blank, const int32_t* total_lens,
+                              const int32_t* chunk_lens, int32_t* labels, int32_t* label_frames, int cap, int32_t* fresh,
+                              void* state, int N, void* stream);
+
 /* ---- post_process/ctc_beam_decoder.py ------------------------------------ */
 
 size_t ms_ctc_beam_workspace_bytes(int T, int N, int V, int beam_width);
@@ -411,6 +436,18 @@ int ms_ctc_beam_decode(const float* probs, const int32_t* lens, int32_t* out_idx
                        int t_begin, int t_end, const float* lm_factor, int finish, int32_t* beam_len,
                        int32_t* beam_idx, int32_t* beam_plen, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* ms_ctc_beam_decode over a WINDOW of the clip's rows (a streaming caller holds only the rows of the current chunk):
+ * probs [rows_held, N, V] holds rows [row0, row0 + rows_held) of the clip and frame t is read at row t - row0;
+ * row0 <= t_begin and t_end - row0 <= rows_held.  T stays the clip's total number of frames (it sizes the trie in the
+ * workspace and out_idx / beam_idx), every stream is present in every window (ended ones are skipped through lens), and
+ * everything else is ms_ctc_beam_decode, which is the row0 = 0, rows_held = T case of the same code.  finish != 0 with
+ * t_begin == t_end writes the current best prefix without disturbing the search. */
+int ms_ctc_beam_decode_rows(const float* probs, const int32_t* lens, int32_t* out_idx, int32_t* out_len, int T, int N,
+                            int V, int blank, int beam_width, float prune_threshold, int separator,
+                            const float* word_factor, int t_begin, int t_end, int row0, int rows_held,
+                            const float* lm_factor, int finish, int32_t* beam_len, int32_t* beam_idx, int32_t* beam_plen,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- feature front-end: data/preprocess.py + builders/pre_process_step.py ---- */
 

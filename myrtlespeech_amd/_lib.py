@@ -86,12 +86,17 @@ SIGNATURES = {
     "ms_ctc_loss_backward_workspace_bytes": (c_size_t, [c_int] * 4),
     "ms_ctc_loss_backward": (c_int, [_P] * 7 + [c_int] * 6 + [_P, c_size_t, _P]),
     "ms_ctc_greedy_decode": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "ms_ctc_greedy_stream_state_bytes": (c_size_t, [c_int]),
+    "ms_ctc_greedy_stream_begin": (c_int, [_P, c_int, _P]),
+    "ms_ctc_greedy_stream_step": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, _P]),
     "ms_embedding_forward": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "ms_rnnt_joint_forward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "ms_rnnt_topk": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "ms_ctc_beam_workspace_bytes": (c_size_t, [c_int] * 4),
     "ms_ctc_beam_decode": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P, c_int, c_int,
                                    _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "ms_ctc_beam_decode_rows": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P, c_int, c_int,
+                                        c_int, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "ms_rnnt_decode_workspace_bytes": (c_size_t, [c_int] * 10),
     "ms_rnnt_decode": (c_int, [_P, _P, _P, _PP, _PP, _PP, _PP, _P, _P, _P, _P, _P, _P] + [c_int] * 10 + [_P, c_size_t, _P]),
     "ms_mfcc_workspace_bytes": (c_size_t, [c_int] * 5),

@@ -645,6 +645,20 @@ class ChunkedDeepSpeech2:
                 self._graph_sig = psig
         self._stream = _ContextStream(self.model, int(lens_cpu.numel()), total, lens_cpu, hx)
 
+    @property
+    def out_lens(self) -> torch.Tensor:
+        """Host int64 ``[N]``: logit rows each utterance of the batch begun will have got when it has been pushed whole."""
+        if self._stream is None:
+            raise RuntimeError("call begin(lens) first")
+        return self._stream.out_lens.clone()
+
+    @property
+    def total_out(self) -> int:
+        """Logit rows the pushes of the batch begun add up to (``logits.shape[0]`` of the full-utterance forward)."""
+        if self._stream is None:
+            raise RuntimeError("call begin(lens) first")
+        return self._stream.total_out
+
     def push(self, chunk: Optional[torch.Tensor], final: bool = False) -> Optional[torch.Tensor]:
         """Feed the next input frames of every utterance of the batch (``[N, C, F, frames]``; utterances that have ended
         get whatever padding the caller has -- it is masked like cnn.py:425-443) and receive the logit rows that became
