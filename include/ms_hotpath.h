@@ -285,7 +285,11 @@ int ms_rnn_layer_is_wide(int cell, int H, int ndir, int N);
  * chained -- the same bits -- for rows that all exist (not MS_RNN_PACKED_ROWS).  packed_host: HOST array of the nl layers'
  * packed weights (device pointers, layer 0 first; layer 0 packed for In, the others for ndir * H); h0 / c0 / hn / cn:
  * [nl * ndir, N, H]; out: [T, N, ndir * H] float32 of the last layer.  ms_rnn_stack_overlap_ok says whether a stack qualifies
- * (MS_RNN_OVERLAP=0: never).  Not for use inside a stream capture or beside another stream's persistent launches. */
+ * (MS_RNN_OVERLAP=0: never); its T is the number of steps the call will RUN -- the max_len handed to ms_rnn_stack_forward, not
+ * the length T of the buffers: a segment must be shorter than the steps that run, so a long buffer holding short sequences
+ * does not qualify (ms_rnn_stack_forward checks with max_len and refuses such a call).  A stack it accepts runs with any
+ * `segments` >= 2: where no cut of about max_len / segments steps qualifies, the forward uses the one the predicate found.
+ * Not for use inside a stream capture or beside another stream's persistent launches. */
 int ms_rnn_stack_overlap_ok(int cell, int T, int N, int In, int H, int ndir, int nl);
 int ms_rnn_stack_forward(int cell, const void* const* packed_host, const float* x, const int32_t* lens, int max_len,
                          const float* h0, const float* c0, float* out, float* hn, float* cn, int T, int N, int In, int H, int ndir,

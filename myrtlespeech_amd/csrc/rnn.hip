@@ -3043,7 +3043,10 @@ extern "C" int ms_rnn_stack_forward(int cell, const void* const* packed_host, co
   const int steps = max_len;
   const size_t GH = (size_t)4 * H;
   const int NG = (int)(ndir * GH);                       // projection columns (both directions' gates)
-  const int SL = overlap_segment_steps(steps, N, NG, segments);      // steps per segment
+  // steps per segment: about steps / segments where such a cut qualifies, otherwise the cut ms_rnn_stack_overlap_ok accepted
+  // (it decides with 8 segments; a stack it said yes to runs whatever `segments` asks for -- the bits do not depend on the cut)
+  int SL = overlap_segment_steps(steps, N, NG, segments);
+  if (SL <= 0) SL = overlap_segment_steps(steps, N, NG, 8);
   MS_REQUIRE(SL > 0, "no time segmentation of this stack qualifies (ask ms_rnn_stack_overlap_ok with T = max_len)");
   const int S = std::max(1, steps / SL);                 // the last segment takes the remainder (SL <= its length < 2 SL)
   const WsLayout W = ws_layout(cell, T, N, H, ndir, std::max(In, ndir * H));

@@ -195,7 +195,7 @@ def run_layers(cell: int, x: torch.Tensor, lens_dev: Optional[torch.Tensor], max
     state_ok = all(s_ is None or (s_.is_contiguous() and tuple(s_.shape) == (nl * ndir, n, hidden)) for s_ in (h0, c0))
     if (nl > 1 and chain and not padded and not pack_rows and _OVERLAP and _lib.issue_point is None and state_ok
             and not torch.cuda.is_current_stream_capturing()
-            and lib.ms_rnn_stack_overlap_ok(cell, t, n, x.shape[2], hidden, ndir, nl)):
+            and lib.ms_rnn_stack_overlap_ok(cell, max_len, n, x.shape[2], hidden, ndir, nl)):      # (the steps that run, not the buffer's t)
         pks = [packed[layer].get(cell, in_sizes[layer], hidden, layer_params[layer], None) for layer in range(nl)]
         arr = (ctypes.c_void_p * nl)(*[pk.data_ptr() for pk in pks])
         out = torch.empty((t, n, ndir * hidden), dtype=torch.float32, device="cuda")

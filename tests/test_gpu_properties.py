@@ -147,3 +147,77 @@ def test_two_batch_groups_in_one_launch_give_the_bits_of_their_own_launches(kind
         assert torch.equal(ys, yw[:t, sl]), (kind, H, N, a, float((ys - yw[:t, sl]).abs().max()))
         assert float(yw[t:, sl].abs().max()) == 0.0 if t < yw.shape[0] else True
         assert torch.equal(hs, hw[:, sl]) and (not lstm or torch.equal(cs, cw[:, sl]))
+
+
+# ----------------------------------------------------------------------------- clips much shorter than the buffer
+@pytest.fixture(scope="module")
+def setup_short():
+    """The same model and buffer with lengths from 101 frames up: the later shards of a sorted batch then hold only clips far
+    shorter than the buffer they travel in (``parallel.shard_batch`` narrows the batch and keeps the time padding), so their
+    recurrent stack runs fewer steps than its buffer has -- down to fewer than one time segment of the overlapped schedule."""
+    from myrtlespeech_amd.post_process.ctc_greedy_decoder import CTCGreedyDecoder
+    model = bench.build_model()
+    g = torch.Generator().manual_seed(199)
+    x = torch.randn(32, 1, 80, 1001, generator=g)
+    lens = torch.sort(torch.randint(101, 1002, (32,), generator=g), descending=True).values
+    lens[0] = 1001
+    (y, ol), _ = model((x.clone(), lens))
+    return model, CTCGreedyDecoder(28), x, lens, y, ol
+
+
+def test_shards_of_short_clips_reproduce_the_whole_batch_bit_for_bit(setup_short):
+    """``test_shards_reproduce_the_whole_batch_bit_for_bit`` with lengths from 101 frames: a shard of 4 whose longest clip has
+    at most 512 frames (256 steps after the convolutions, one 256-step segment of the overlapped stack) must take the layer
+    loop, not raise, and still give the whole batch's rows."""
+    from myrtlespeech_amd.parallel import shard_batch
+    model, dec, x, lens, y, ol = setup_short
+    whole = dec(y, ol)
+    assert int(lens[-4]) <= 512          # (the last shard of 8 is on the short side of the gate)
+    for world in (2, 4, 8):
+        hyps, row = [], 0
+        for rank in range(world):
+            xs, ls = shard_batch(x, lens, world, rank)
+            (ys, ols), _ = model((xs.clone(), ls))
+            t = ys.shape[0]
+            diff = (ys - y[:t, row:row + ls.numel()]).abs()
+            assert torch.equal(ys, y[:t, row:row + ls.numel()]), (world, rank, float(diff.max()))
+            assert torch.equal(ols.cpu(), ol[row:row + ls.numel()].cpu())
+            hyps += dec(ys, ols)
+            row += ls.numel()
+        assert hyps == whole
+
+
+def test_a_longer_buffer_changes_nothing(setup_short):
+    """The whole batch in a buffer of 1401 frames (zeros appended, the same lengths): the logits of the frames the shorter
+    buffer has are the same bits, and beyond them every utterance shows the constant FC response to a zero vector."""
+    model, dec, x, lens, y, ol = setup_short
+    longer = torch.cat([x, torch.zeros(32, 1, 80, 400)], dim=3)
+    (y2, ol2), _ = model((longer, lens))
+    t = y.shape[0]
+    assert y2.shape[0] > t and torch.equal(ol2.cpu(), ol.cpu())
+    assert torch.equal(y2[:t], y)
+    const = y[ol[-1].item():, -1][:1]            # the shortest utterance's padded tail
+    assert const.shape[0] == 1
+    assert torch.equal(y2[t:], const[None].expand_as(y2[t:]))
+    assert dec(y2, ol2) == dec(y, ol)
+
+
+def test_short_clips_in_a_long_buffer_equal_the_same_clips_in_a_short_one(setup_short):
+    """32 clips of 41 .. 63 frames (at most 32 steps after the convolutions' time stride of 2 x 1: not more than one 32-step
+    segment of the overlapped stack) in the 1001-frame buffer against the same clips in a buffer of 64 frames.  The lengths are
+    odd: the reference's ``out_lens`` counts the SAME padding of the BUFFER (10 columns for an even buffer, 11 for an odd one),
+    so a clip of an even length gets one output step more in the odd buffer than in the even one (64 frames: 33 against 32) --
+    with odd lengths both buffers give every clip (L + 1) / 2 steps, and the frames of a clip see the same 5 columns to their
+    left either way."""
+    model, dec, x, _, _, _ = setup_short
+    g = torch.Generator().manual_seed(41)
+    lens = torch.sort(2 * torch.randint(20, 32, (32,), generator=g) + 1, descending=True).values
+    lens[0] = 63
+    assert int(lens.min()) >= 41 and int(lens.max()) == 63
+    (ya, ola), _ = model((x[..., :64].contiguous(), lens))
+    (yb, olb), _ = model((x.clone(), lens))
+    t = ya.shape[0]
+    assert t == 32 and yb.shape[0] == 501 and int(olb.max()) == 32 and torch.equal(ola.cpu(), olb.cpu())
+    assert torch.equal(yb[:t], ya)
+    assert torch.equal(yb[t:], yb[t:t + 1].expand_as(yb[t:]))      # nothing but the FC's response to zero past the last step
+    assert dec(ya, ola) == dec(yb, olb)
