@@ -453,6 +453,56 @@ int ms_ctc_beam_decode_rows(const float* probs, const int32_t* lens, int32_t* ou
                             const float* lm_factor, int finish, int32_t* beam_len, int32_t* beam_idx, int32_t* beam_plen,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- n-gram language model (myrtlespeech_amd/language_model.py) ----------- */
+
+/* A word-level back-off n-gram model as ONE contiguous little-endian blob, packed for one lm_weight by
+ * NGramLanguageModel.packed and walked identically by NGramLanguageModel.factor (host) and csrc/ngram_lm.h (device):
+ *
+ *   header, 16 uint32 words (64 bytes):
+ *     0 magic 0x4D4C534D ("MSLM")   1 order (1 .. MS_NGRAM_MAX_ORDER)   2 log2(vocabulary slots)   3 log2(n-gram slots)
+ *     4, 5 vocabulary hash seed (lo, hi)   6, 7 n-gram hash seed (lo, hi)   8 id of <s> (int32, -1: none)   9 id of <unk>
+ *     10 longest probe run of the vocabulary table   11 ... of the n-gram table (slots examined to reach any stored key)
+ *     12 byte offset of the vocabulary table   13 ... of the n-gram table (multiples of 16)   14 size of the blob   15 words
+ *   vocabulary table, 16 bytes per slot: {uint64 key, int32 word id, 0}; key = fin(h), h = step(...step(seed, s1)..., sk)
+ *     over the word's symbols s1 .. sk
+ *   n-gram table, 16 bytes per slot: {uint64 key, float32 p ** lm_weight, float32 backoff ** lm_weight} (1.0 where the
+ *     file gives no back-off); key = fin(step(h, n)), h = step(...step(seed, id1)..., idn) over the n word ids
+ *   step(h, x) = (h ^ (x + 1)) * 0x100000001B3 mod 2^64;  fin = the 64-bit murmur3 finaliser, 0 mapped to 1.
+ *
+ * Open addressing, power-of-two slot counts, load <= 0.5, linear probing from key & (slots - 1); key 0 = empty slot.  A
+ * look-up examines at most the recorded number of slots, so a damaged table cannot keep a kernel from ending.  Keys are
+ * compared in full and no two stored keys are equal (the packer re-seeds until so); a spelling outside the vocabulary
+ * that hashes onto a stored key (probability ~ words / 2^64) is scored as that word, on the host and the device alike.
+ *
+ * The factor of a prefix: drop one trailing separator, split on runs of the separator; the scored word w is what follows
+ * the last separator (none: the factor is 1.0), the context the up-to-(order - 1) words before it, preceded by <s> when
+ * fewer exist and the model has <s>; unknown spellings are <unk>.  Then, starting from float32 1 and rounding after every
+ * multiply: for k = context length down to 0, if (last k context words, w) is stored multiply by its p-factor and stop;
+ * else if k > 0 and (last k context words) is stored multiply by its backoff-factor. */
+#define MS_NGRAM_MAX_ORDER 5
+
+/* Host-only validation of a packed blob (magic, order, slot counts, offsets and sizes inside `bytes`, probe bounds <=
+ * slots, special ids < words); runs without a GPU.  MS_OK or MS_ERR_INVALID (ms_last_error says what). */
+int ms_ngram_lm_table_check(const void* blob_host, size_t bytes);
+
+/* Scores P prefixes against a table: prefixes [P, L] int32 padded, prefix_lens [P], out [P] float32 = the factor defined
+ * above.  table: the blob in device memory; header_host: its first 64 bytes in HOST memory (re-validated here against
+ * table_bytes; the device copy is never read by the host). */
+int ms_ngram_lm_score(const void* table, const void* header_host, size_t table_bytes, const int32_t* prefixes,
+                      const int32_t* prefix_lens, float* out, int P, int L, int separator, void* stream);
+
+/* ms_ctc_beam_decode_rows with the language model in device memory: the separator extension of beam entry l is
+ * multiplied by the factor of l + (separator,) looked up inside the frame loop (computed at most once per prefix), so a
+ * decode with a model is one launch.  lm_table / lm_header_host / lm_table_bytes as for ms_ngram_lm_score; separator >= 0.
+ * The workspace (ms_ctc_beam_lm_workspace_bytes; t_begin = 0 initialises it) additionally carries every prefix's model
+ * state, so a decode advanced in pieces equals the decode in one call.  Everything else as ms_ctc_beam_decode_rows. */
+size_t ms_ctc_beam_lm_workspace_bytes(int T, int N, int V, int beam_width, int order);
+int ms_ctc_beam_decode_lm(const float* probs, const int32_t* lens, int32_t* out_idx, int32_t* out_len, int T, int N,
+                          int V, int blank, int beam_width, float prune_threshold, int separator,
+                          const float* word_factor, int t_begin, int t_end, int row0, int rows_held, const void* lm_table,
+                          const void* lm_header_host, size_t lm_table_bytes, int finish, int32_t* beam_len,
+                          int32_t* beam_idx, int32_t* beam_plen, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- feature front-end: data/preprocess.py + builders/pre_process_step.py ---- */
 
 /* torchaudio.transforms.MFCC as built by builders/pre_process_step.py:33-43 (torchaudio==0.4.0,

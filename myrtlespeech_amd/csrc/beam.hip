@@ -26,12 +26,14 @@
 #include <algorithm>
 
 #include "common.h"
+#include "ngram_lm.h"
 
 namespace {
 
 constexpr int HDR_INTS = 16;
 enum { F_PRESENT = 1, F_KEPT = 2 };
 constexpr size_t BEAM_LDS_LIMIT = 150 * 1024;
+static_assert(ms_lm::HIST == 4, "a node's word history is stored as one int4");
 
 // bytes of the per-utterance working arrays (LDS; the workspace's scratch region when they do not fit)
 size_t beam_lds_bytes(int V, int W) {
@@ -46,7 +48,15 @@ struct BeamLayout {
   int NN, CS, M, big;
 };
 
-BeamLayout beam_layout(int T, int V, int W) {
+// Device language model (ms_ctc_beam_decode_lm): the table and, per utterance and BEHIND everything above (whose offsets and
+// sizes do not change), every trie node's model state -- the running hash of the symbols since the last separator, the ids
+// of the last complete words, and the factor of `node + separator` once some frame has needed it (ngram_lm.h: NOT_COMPUTED)
+struct BeamLm {
+  ms_lm::Tab tab;
+  size_t node_hash, node_hist, node_fac;
+};
+
+BeamLayout beam_layout(int T, int V, int W, BeamLm* lm = nullptr) {
   BeamLayout L;
   L.M = W * (V + 1);
   L.NN = 2 + T * W;          // a frame makes at most W nodes (the extensions that enter the beam)
@@ -69,7 +79,12 @@ BeamLayout beam_layout(int T, int V, int W) {
   L.node_nw = take((size_t)L.NN * 4);
   L.node_cslot = take((size_t)L.NN * 4);
   L.childtab = take((size_t)L.CS * V * 4);
-  L.scratch = take(L.big ? beam_lds_bytes(V, W) : 0);
+  L.scratch = take(L.big ? beam_lds_bytes(V, W) + (lm ? (size_t)2 * W * 4 : 0) : 0);      // (+ bm_fac with a model)
+  if (lm) {
+    lm->node_hash = take((size_t)L.NN * 8);
+    lm->node_hist = take((size_t)L.NN * ms_lm::HIST * 4);
+    lm->node_fac = take((size_t)L.NN * 4);
+  }
   L.per_utt = ms::align_up(o, 256);
   return L;
 }
@@ -88,6 +103,7 @@ struct BeamP {
   BeamLayout L;
   int T, N, V, W, blank, sep, t_begin, t_end, finish, stamps;
   float thr;
+  BeamLm lm;   // (last: the fields above keep their places in the kernel argument)
 };
 
 // MS_PIN(x): an empty asm that "modifies" x -- the load that produced x is issued where it is written.  hipcc otherwise sinks an
@@ -119,7 +135,8 @@ __device__ __forceinline__ int find_in_beam(const int* bmn, int W8, int node) {
 // BIG: beam_width * (alphabet + 1) too large for the LDS (~2 300 candidates; 84 prefixes at V = 29) -- the same code
 // with its working arrays in the workspace.  Slow (every phase goes through L2) but any width up to 256 decodes.
 // MS_BEAM_STAMPS=1 (read per call): thread 0 of utterance 0 accumulates the 100 MHz wall clock per barrier-separated phase of
-// the frame loop into hdr[4 .. 4 + 8] (ticks summed over the call's frames; tools/beam_stamps.py prints them)
+// the frame loop into hdr[4 .. 4 + 8] (ticks summed over the call's frames; tools/beam_stamps.py prints them); hdr[12] is the
+// language-model phase S0 of the LM instantiations (tools/beam_lm_time.py)
 #define MS_BEAM_STAMP_BEGIN() do { if (stamping) st_prev = wall_clock64(); } while (0)
 #define MS_BEAM_STAMP(k) do { if (stamping) { const unsigned long long now_ = wall_clock64(); st_acc[k] += (unsigned)(now_ - st_prev); st_prev = now_; } } while (0)
 
@@ -128,7 +145,9 @@ __device__ __forceinline__ int find_in_beam(const int* bmn, int W8, int node) {
 // frame loop keeps live (106 SGPRs, part of them spilled to VGPR lanes and fetched with v_readlane: DESIGN 9.3 of round 5)
 // become immediate offsets of the LDS instructions, and the divisions by V constant multiplications.  Instantiated for the
 // reference's decode size -- 29 symbols (configs/deep_speech_2_en.config), width 8; the arithmetic is untouched.
-template <bool BIG, int NT, int VC = 0, int WC = 0>
+// LM: the separator extension's factor comes from the n-gram table in device memory (ngram_lm.h) instead of `lm_factor`.
+// Every addition is under `if constexpr (LM)`; the instantiations without it are what they were.
+template <bool BIG, int NT, int VC = 0, int WC = 0, bool LM = false>
 __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int tid = threadIdx.x, n = blockIdx.x;
@@ -161,7 +180,8 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
   int* par_rank = reinterpret_cast<int*>(par_val + W);
   int* newbeam = par_rank + W;
   int* ent_fresh = newbeam + W;
-  int* sh = ent_fresh + W;  // [0]=B, [1]=k_count, [2]=n_nodes, [3]=n_cslots
+  int* sh = ent_fresh + W;  // [0]=B, [1]=k_count, [2]=n_nodes, [3]=n_cslots, [4]=factors computed (LM)
+  float* bm_fac = reinterpret_cast<float*>(sh + 8);           // [2][W] (LM only): the model's factor for beam entry + separator
 
   // ---- global state of this utterance
   int* hdr = reinterpret_cast<int*>(u + p.L.hdr);
@@ -179,6 +199,14 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
   int* node_nw = reinterpret_cast<int*>(u + p.L.node_nw);
   int* node_cslot = reinterpret_cast<int*>(u + p.L.node_cslot);
   int* childtab = reinterpret_cast<int*>(u + p.L.childtab);
+  unsigned long long* node_hash = nullptr;
+  int4* node_hist = nullptr;
+  float* node_fac = nullptr;
+  if constexpr (LM) {
+    node_hash = reinterpret_cast<unsigned long long*>(u + p.lm.node_hash);
+    node_hist = reinterpret_cast<int4*>(u + p.lm.node_hist);
+    node_fac = reinterpret_cast<float*>(u + p.lm.node_fac);
+  }
 
   // a thread's first (usually only) candidate / row entry is (tid / V, tid % V) in every frame: the integer division -- ~40
   // instructions each in S1 and S6 -- is done once
@@ -196,13 +224,17 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
       bm_node[b0 * W8] = 0; bm_pb[b0 * W] = 1.0f; bm_pnb[b0 * W] = 0.0f;
       bm_last[b0 * W] = -1; bm_len[b0 * W] = 0; bm_nw[b0 * W] = 0; bm_cslot[b0 * W] = 0;
       sh[0] = 1; sh[2] = 1; sh[3] = 1;
+      if constexpr (LM) {      // the root: no word begun, <s> (if the model has one) as history; `() + separator` scores no word
+        node_hash[0] = p.lm.tab.vocab_seed; node_hist[0] = make_int4(-1, -1, -1, p.lm.tab.bos); node_fac[0] = 1.0f;
+        bm_fac[b0 * W] = 1.0f; sh[4] = 0;
+      }
     }
     for (int v = tid; v < V; v += NT) {
       childtab[v] = -1;
       lc_node[b0 * WV + v] = -1; lc_cslot[b0 * WV + v] = -1; lc_tidx[b0 * WV + v] = -1;
     }
   } else {
-    if (tid == 0) { sh[0] = hdr[2]; sh[2] = hdr[0]; sh[3] = hdr[1]; }
+    if (tid == 0) { sh[0] = hdr[2]; sh[2] = hdr[0]; sh[3] = hdr[1]; if constexpr (LM) sh[4] = hdr[13]; }
     const int B_in = hdr[2];
     for (int w = tid; w < W; w += NT)
       if (w < B_in) {
@@ -210,6 +242,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
         bm_node[b0 * W8 + w] = nd; bm_pb[b0 * W + w] = g_beam_pb[w]; bm_pnb[b0 * W + w] = g_beam_pnb[w];
         bm_last[b0 * W + w] = node_sym[nd]; bm_len[b0 * W + w] = node_len[nd]; bm_nw[b0 * W + w] = node_nw[nd];
         bm_cslot[b0 * W + w] = node_cslot[nd];
+        if constexpr (LM) bm_fac[b0 * W + w] = node_fac[nd];
       }
     for (int i = tid; i < M; i += NT) { c_pb[(b0 ^ 1) * M + i] = tbl_pb[i]; c_pnb[(b0 ^ 1) * M + i] = tbl_pnb[i]; }
     for (int i = tid; i < WV; i += NT) {
@@ -253,6 +286,29 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
     // compare and not a lane mask evaluated under one loop's EXEC and read under another's -- tools/isa_lanemask_audit.py)
     const float p_blank = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(prow[p.blank])));
 
+    // ---- S0 (LM): the model is consulted only in a frame whose separator survives pruning -- one word for the whole
+    // workgroup, so the branch and its barrier are uniform -- and only for the entries that do not end in the separator (a
+    // repeated separator takes the repeat branch below).  One lane per entry, all entries' probes in flight together; an
+    // entry whose node has been scored before (this frame's beam carries the node's factor along) costs nothing.
+    if constexpr (LM) {
+      const float p_sep = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(prow[p.sep])));
+      if (!(p_sep <= p.thr)) {
+        for (int w = tid; w < B; w += NT) {
+          if (bml[w] != p.sep && bm_fac[cb * W + w] < 0.f) {
+            const int nd = bmn[w];
+            const unsigned long long h = node_hash[nd];
+            const int4 hs = node_hist[nd];
+            const int hist[ms_lm::HIST] = {hs.x, hs.y, hs.z, hs.w};
+            const float f = ms_lm::factor(p.lm.tab, h, hist);
+            node_fac[nd] = f; bm_fac[cb * W + w] = f;
+            atomicAdd(&sh[4], 1);
+          }
+        }
+        __syncthreads();
+      }
+      MS_BEAM_STAMP(8);      // (S0 alone: S1's slot starts here)
+    }
+
     // (S2's words that do not depend on S1 are requested here, ahead of S1 and its barrier)
     const int s2_w = tid;                                   // W <= NT is not assumed: the S2 loop below re-reads for w >= NT
     float s2_pb = 0.f, s2_pnb = 0.f, s2_plast = 0.f;
@@ -275,6 +331,8 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
       MS_PIN(pc); MS_PIN(child); MS_PIN(ti); MS_PIN(len_w); MS_PIN(last_w);
       float pb_w = bmpb[w], pnb_w = bmpnb[w];
       MS_PIN(pb_w); MS_PIN(pnb_w);
+      float fac_w = 1.0f;
+      if constexpr (LM) { fac_w = bm_fac[cb * W + w]; MS_PIN(fac_w); }
       const int w2 = find_in_beam(bmn, W8, child);         // -1 for child == -1 (node ids are >= 0, non-members hold -2)
       const int tis = ti >= 0 ? ti : 0;
       float pb_t = c_pb[pp * M + tis], pnb_t = c_pnb[pp * M + tis];
@@ -283,7 +341,11 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
       if (c != p.blank && !(pc <= p.thr)) {  // `if ctc[t][c] <= prune_threshold: continue`
         const bool repeat = len_w > 0 && c == last_w;
         float a = repeat ? pc * pb_w : pc * (pb_w + pnb_w);
-        if (!repeat && p.lm_factor != nullptr && c == p.sep) a = a * p.lm_factor[(size_t)n * W + w];
+        if constexpr (LM) {
+          if (!repeat && c == p.sep) a = a * fac_w;
+        } else {
+          if (!repeat && p.lm_factor != nullptr && c == p.sep) a = a * p.lm_factor[(size_t)n * W + w];
+        }
         if (w2 >= 0) {  // l_plus in A_prev: only Pnb[t][l_plus] += a
           par_val[w2] = a; par_rank[w2] = i * 4; par_present[w2] = 1;
         } else {
@@ -439,6 +501,19 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
           node_nw[nd] = bmnw[w] + ((c == p.sep && bml[w] != p.sep) ? 1 : 0);
           childtab[(size_t)bmcs[w] * V + c] = nd;
           lcn[e] = nd;
+          if constexpr (LM) {      // the node's model state from its parent's: a separator that ends a word looks the word up
+            const int par = bmn[w];
+            unsigned long long h = node_hash[par];
+            const int4 hs = node_hist[par];
+            int hist[ms_lm::HIST] = {hs.x, hs.y, hs.z, hs.w};
+            if (c == p.sep) {
+              if (bmlen[w] > 0 && bml[w] != p.sep) ms_lm::push_word(hist, ms_lm::vocab_id(p.lm.tab, h));
+              h = p.lm.tab.vocab_seed;
+            } else {
+              h = ms_lm::step(h, (unsigned)c);
+            }
+            node_hash[nd] = h; node_hist[nd] = make_int4(hist[0], hist[1], hist[2], hist[3]); node_fac[nd] = ms_lm::NOT_COMPUTED;
+          }
         }
         if (cs < 0) {
           cs = atomicAdd(&sh[3], 1);
@@ -494,6 +569,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
       }
       bm_node[nb * W8 + j] = nd; bm_last[nb * W + j] = last; bm_len[nb * W + j] = ln; bm_nw[nb * W + j] = nw;
       bm_cslot[nb * W + j] = cs; bm_pb[nb * W + j] = c_pb[cp * M + i]; bm_pnb[nb * W + j] = c_pnb[cp * M + i];
+      if constexpr (LM) bm_fac[nb * W + j] = i < W ? bm_fac[cb * W + i] : node_fac[nd];
     }
     for (int j = Bn + tid; j < W8; j += NT) bm_node[nb * W8 + j] = -2;
     if (tid == 0) sh[0] = Bn;
@@ -504,7 +580,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
   // ---- persist state, emit results (the beam and its rows sit in the buffers of the frame the loop stopped at)
   const int eb = t & 1;
   const int B = sh[0];
-  if (tid == 0) { hdr[0] = sh[2]; hdr[1] = sh[3]; hdr[2] = B; }
+  if (tid == 0) { hdr[0] = sh[2]; hdr[1] = sh[3]; hdr[2] = B; if constexpr (LM) hdr[13] = sh[4]; }
   if (stamping)
     for (int k = 0; k < 9; ++k) hdr[4 + k] = (int)st_acc[k];
   for (int i = tid; i < M; i += NT) { tbl_pb[i] = c_pb[(eb ^ 1) * M + i]; tbl_pnb[i] = c_pnb[(eb ^ 1) * M + i]; }
@@ -545,7 +621,7 @@ static int beam_decode_window(const float* probs, const int32_t* lens, int32_t* 
                               int blank, int beam_width, float prune_threshold, int separator, const float* word_factor,
                               int t_begin, int t_end, int row0, int rows_held, const float* lm_factor, int finish,
                               int32_t* beam_len, int32_t* beam_idx, int32_t* beam_plen, void* workspace, size_t workspace_bytes,
-                              void* stream) {
+                              void* stream, const ms_lm::Tab* lm_tab = nullptr) {
   MS_REQUIRE(probs && lens && workspace, "null pointer");
   MS_REQUIRE(T > 0 && N > 0 && V > 0 && beam_width > 0, "bad shape");
   MS_REQUIRE(blank >= 0 && blank < V, "blank out of range");
@@ -556,20 +632,24 @@ static int beam_decode_window(const float* probs, const int32_t* lens, int32_t* 
   MS_REQUIRE(!finish || (out_idx && out_len), "outputs required when finishing");
   MS_REQUIRE((beam_idx == nullptr) == (beam_len == nullptr) && (beam_idx == nullptr) == (beam_plen == nullptr),
              "beam_len/beam_idx/beam_plen go together");
-  const BeamLayout L = beam_layout(T, V, beam_width);
+  BeamLm lm_state{};
+  const BeamLayout L = beam_layout(T, V, beam_width, lm_tab ? &lm_state : nullptr);
   if (workspace_bytes < L.per_utt * (size_t)N) {
     ms::set_error("ms_ctc_beam_decode: workspace too small");
     return MS_ERR_WORKSPACE;
   }
   MS_REQUIRE(beam_width <= 256, "beam_width must not exceed 256");
-  const size_t lds = L.big ? 0 : beam_lds_bytes(V, beam_width);
+  const size_t lds = L.big ? 0 : beam_lds_bytes(V, beam_width) + (lm_tab ? (size_t)2 * beam_width * 4 : 0);
   static ms::DeviceOnce attr_once;
   if (attr_once.need()) {
     MS_HIP(hipFuncSetAttribute((const void*)beam_kernel<false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MS_HIP(hipFuncSetAttribute((const void*)beam_kernel<false, 256, 29, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MS_HIP(hipFuncSetAttribute((const void*)beam_kernel<false, 256, 0, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MS_HIP(hipFuncSetAttribute((const void*)beam_kernel<false, 256, 29, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_once.done();
   }
   BeamP p;
+  p.lm = lm_state;
   // The kernel addresses frame t at probs + t * N * V.  A window's first row is frame row0, so the kernel is handed the address
   // row 0 WOULD have (never dereferenced below row0: t >= t_begin >= row0): a `row0` field subtracted per frame inside the
   // kernel measured +1 .. 2 % on the whole-clip decode at widths 4 and 8 (same-box A/B against the kernel without it), and
@@ -586,6 +666,19 @@ static int beam_decode_window(const float* probs, const int32_t* lens, int32_t* 
   }
   static const int nt_env = getenv("MS_BEAM_THREADS") ? atoi(getenv("MS_BEAM_THREADS")) : 0;      // A/B switch: 64 or 256
   const bool one_wave = nt_env == 64;
+  if (lm_tab) {      // the device language model: the BIG path, the constant-shape twins, the generic kernel
+    p.lm.tab = *lm_tab;
+    p.lm_factor = nullptr;
+    const bool cs = V == 29 && !(getenv("MS_BEAM_CONST") && getenv("MS_BEAM_CONST")[0] == '0');
+    if (L.big) hipLaunchKernelGGL((beam_kernel<true, 256, 0, 0, true>), dim3(N), dim3(256), 0, (hipStream_t)stream, p);
+    else if (cs && beam_width == 8) hipLaunchKernelGGL((beam_kernel<false, 256, 29, 8, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+    else if (cs && beam_width == 4) hipLaunchKernelGGL((beam_kernel<false, 256, 29, 4, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+    else if (cs && beam_width == 16) hipLaunchKernelGGL((beam_kernel<false, 256, 29, 16, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+    else if (cs && beam_width == 32) hipLaunchKernelGGL((beam_kernel<false, 256, 29, 32, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((beam_kernel<false, 256, 0, 0, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+    MS_LAUNCH_CHECK();
+    return MS_OK;
+  }
   if (L.big) hipLaunchKernelGGL((beam_kernel<true, 256>), dim3(N), dim3(256), 0, (hipStream_t)stream, p);
   else if (one_wave && lds <= 64 * 1024) hipLaunchKernelGGL((beam_kernel<false, 64>), dim3(N), dim3(64), lds, (hipStream_t)stream, p);
   else if (V == 29 && beam_width == 8 && !(getenv("MS_BEAM_CONST") && getenv("MS_BEAM_CONST")[0] == '0'))
@@ -621,4 +714,27 @@ extern "C" int ms_ctc_beam_decode_rows(const float* probs, const int32_t* lens, 
   return beam_decode_window(probs, lens, out_idx, out_len, T, N, V, blank, beam_width, prune_threshold, separator, word_factor,
                             t_begin, t_end, row0, rows_held, lm_factor, finish, beam_len, beam_idx, beam_plen, workspace,
                             workspace_bytes, stream);
+}
+
+// ---- the same search with an n-gram language model resident on the device (ngram_lm.h)
+extern "C" size_t ms_ctc_beam_lm_workspace_bytes(int T, int N, int V, int beam_width, int order) {
+  if (T <= 0 || N <= 0 || V <= 0 || beam_width <= 0 || order < 1 || order > ms_lm::MAX_ORDER) return 0;
+  BeamLm lm{};
+  return beam_layout(T, V, beam_width, &lm).per_utt * (size_t)N;
+}
+
+extern "C" int ms_ctc_beam_decode_lm(const float* probs, const int32_t* lens, int32_t* out_idx, int32_t* out_len, int T, int N,
+                                     int V, int blank, int beam_width, float prune_threshold, int separator,
+                                     const float* word_factor, int t_begin, int t_end, int row0, int rows_held,
+                                     const void* lm_table, const void* lm_header_host, size_t lm_table_bytes, int finish,
+                                     int32_t* beam_len, int32_t* beam_idx, int32_t* beam_plen, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  MS_REQUIRE(lm_table != nullptr, "null language-model table");
+  MS_REQUIRE(separator >= 0, "a language model needs a separator");
+  const char* bad = ms_lm::header_problem(lm_header_host, lm_table_bytes);
+  MS_REQUIRE(bad == nullptr, bad ? bad : "");
+  const ms_lm::Tab tab = ms_lm::make_tab(lm_header_host, lm_table);
+  return beam_decode_window(probs, lens, out_idx, out_len, T, N, V, blank, beam_width, prune_threshold, separator, word_factor,
+                            t_begin, t_end, row0, rows_held, nullptr, finish, beam_len, beam_idx, beam_plen, workspace,
+                            workspace_bytes, stream, &tab);
 }

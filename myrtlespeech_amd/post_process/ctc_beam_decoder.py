@@ -10,13 +10,26 @@ A ``language_model`` is a host callable, so with one set the kernel is advanced 
 frame at a time and the host supplies, per beam entry, the factor
 ``float32(lm(prefix + (separator,)) ** lm_weight)`` the reference multiplies in at
 ctc_beam_decoder.py:222-228; without one the whole utterance is a single launch.
+
+An ``NGramLanguageModel`` (myrtlespeech_amd/language_model.py) is the exception: its table lives in device memory and
+the kernel looks the factor up itself, so the decode is a single launch with a model as well.
 """
+import ctypes
 from typing import Callable, List, Optional, Tuple
 
 import torch
 
 from myrtlespeech_amd import _lib
+from myrtlespeech_amd.language_model import NGramLanguageModel
 from myrtlespeech_amd.post_process._common import check_decoder_args, ragged_to_lists
+
+
+def check_device_language_model(lm: NGramLanguageModel, separator_index: Optional[int], symbols: Optional[int]) -> None:
+    """The model's separator and alphabet must be the decoder's / the input's."""
+    if separator_index is not None and lm.separator_index != separator_index:
+        raise ValueError(f"language_model.separator_index={lm.separator_index} and separator_index={separator_index} differ")
+    if symbols is not None and len(lm.alphabet) != symbols:
+        raise ValueError(f"language_model has an alphabet of {len(lm.alphabet)} symbols, the input has {symbols}")
 
 
 class CTCBeamDecoder(torch.nn.Module):
@@ -35,6 +48,8 @@ class CTCBeamDecoder(torch.nn.Module):
             raise ValueError("lm_weight must be set when using language_model")
         if separator_index is not None and separator_index < 0:
             raise ValueError(f"separator_index={separator_index} must be >= 0")
+        if isinstance(language_model, NGramLanguageModel):
+            check_device_language_model(language_model, separator_index, None)
         super().__init__()
         self.blank_index = blank_index
         self.beam_width = beam_width
@@ -79,6 +94,19 @@ class CTCBeamDecoder(torch.nn.Module):
 
         if not use_lm:
             call(0, seq_len, None, 1)
+            return ragged_to_lists(out_idx, out_len)
+
+        if isinstance(self.language_model, NGramLanguageModel):
+            # the model is a table in device memory: one launch, nothing read back, no host call per beam entry
+            lm = self.language_model
+            check_device_language_model(lm, self.separator_index, symbols)
+            table, blob = lm.device_table(self.lm_weight)
+            ws = self._workspace.get(lib.ms_ctc_beam_lm_workspace_bytes(seq_len, batch, symbols, w, lm.order))
+            _lib.check(lib.ms_ctc_beam_decode_lm(_lib.ptr(xd), _lib.ptr(lens_dev), _lib.ptr(out_idx), _lib.ptr(out_len),
+                                                 seq_len, batch, symbols, self.blank_index, w, float(self.prune_threshold),
+                                                 sep, _lib.ptr(wf), 0, seq_len, 0, seq_len, _lib.ptr(table),
+                                                 ctypes.c_void_p(blob.ctypes.data), blob.size, 1, None, None, None,
+                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "ms_ctc_beam_decode_lm")
             return ragged_to_lists(out_idx, out_len)
 
         # host language model.  The reference consults it for beam entry l at frame t only when the separator extension of l

@@ -12,13 +12,16 @@ between pushes and end with exactly the transcript the whole-clip decoder gives:
 * ``StreamingCTCBeamDecoder``: ``ms_ctc_beam_decode_rows`` over the rows of the push; the search state lives in the
   kernel's workspace as it does between the frames of ``CTCBeamDecoder``'s host-language-model path.  ``best()`` is the
   current best prefix and may change as audio arrives.  A host ``language_model`` is refused: the callback stays with
-  ``CTCBeamDecoder``.
+  ``CTCBeamDecoder``.  An ``NGramLanguageModel`` is taken: its table is in device memory and every prefix's model state
+  in the workspace, so ``ms_ctc_beam_decode_lm`` advances over a push exactly as the model-free search does.
 """
+import ctypes
 from typing import List, Optional
 
 import torch
 
 from myrtlespeech_amd import _lib
+from myrtlespeech_amd.language_model import NGramLanguageModel
 from myrtlespeech_amd.post_process._common import SUPPORTED_LENGTH_DTYPES, check_decoder_args, ragged_to_lists
 
 # layout of ms_ctc_greedy_stream_step's state (include/ms_hotpath.h): int32 words, a header and four words per stream
@@ -154,14 +157,23 @@ class StreamingCTCBeamDecoder:
             raise ValueError(f"prune_threshold={prune_threshold} not in [0.0, 1.0]")
         if separator_index is not None and separator_index < 0:
             raise ValueError(f"separator_index={separator_index} must be >= 0")
-        if language_model is not None or lm_weight is not None:
-            raise ValueError("the streaming beam decoder takes no language_model: the host callback is CTCBeamDecoder's "
-                             "(the reference ships only no_lm)")
+        if isinstance(language_model, NGramLanguageModel):
+            if lm_weight is None:
+                raise ValueError("lm_weight must be set when using language_model")
+            if separator_index is not None and language_model.separator_index != separator_index:
+                raise ValueError(f"language_model.separator_index={language_model.separator_index} and "
+                                 f"separator_index={separator_index} differ")
+        elif language_model is not None or lm_weight is not None:
+            raise ValueError("the streaming beam decoder takes no host language_model (only an NGramLanguageModel, whose "
+                             "table is in device memory): the host callback is CTCBeamDecoder's")
         self.blank_index = blank_index
         self.beam_width = beam_width
         self.prune_threshold = prune_threshold
         self.separator_index = separator_index
         self.word_weight = word_weight
+        # as in the reference, a model without a separator is never consulted
+        self.language_model = language_model if separator_index is not None else None
+        self.lm_weight = lm_weight
         self._lens = None
 
     def begin(self, lens: torch.Tensor, total_frames: int) -> None:
@@ -193,6 +205,15 @@ class StreamingCTCBeamDecoder:
 
     def _call(self, window, t0, t1, row0, finish):
         sep = -1 if self.separator_index is None else int(self.separator_index)
+        if self.language_model is not None:
+            table, blob = self.language_model.device_table(self.lm_weight)
+            _lib.check(_lib.load().ms_ctc_beam_decode_lm(
+                _lib.ptr(window), _lib.ptr(self._lens), _lib.ptr(self._out_idx), _lib.ptr(self._out_len), self._total,
+                self._n, self._symbols, self.blank_index, self.beam_width, float(self.prune_threshold), sep,
+                _lib.ptr(self._wf), t0, t1, row0, window.shape[0], _lib.ptr(table), ctypes.c_void_p(blob.ctypes.data),
+                blob.size, finish, None, None, None, _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr()),
+                "ms_ctc_beam_decode_lm")
+            return
         _lib.check(_lib.load().ms_ctc_beam_decode_rows(
             _lib.ptr(window), _lib.ptr(self._lens), _lib.ptr(self._out_idx), _lib.ptr(self._out_len), self._total, self._n,
             self._symbols, self.blank_index, self.beam_width, float(self.prune_threshold), sep, _lib.ptr(self._wf), t0, t1,
@@ -211,7 +232,14 @@ class StreamingCTCBeamDecoder:
             raise ValueError(f"{self._t + r} rows pushed, total_frames={self._total}")
         if self._symbols is None:
             self._symbols = symbols
-            nbytes = _lib.load().ms_ctc_beam_workspace_bytes(self._total, n, symbols, self.beam_width)
+            if self.language_model is not None:
+                if len(self.language_model.alphabet) != symbols:
+                    raise ValueError(f"language_model has an alphabet of {len(self.language_model.alphabet)} symbols, "
+                                     f"probs_rows has {symbols}")
+                nbytes = _lib.load().ms_ctc_beam_lm_workspace_bytes(self._total, n, symbols, self.beam_width,
+                                                                    self.language_model.order)
+            else:
+                nbytes = _lib.load().ms_ctc_beam_workspace_bytes(self._total, n, symbols, self.beam_width)
             self._ws = torch.zeros(max(int(nbytes), 256), dtype=torch.uint8, device="cuda")
         elif symbols != self._symbols:
             raise ValueError(f"probs_rows has {symbols} symbols, earlier pushes had {self._symbols}")

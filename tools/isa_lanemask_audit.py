@@ -35,7 +35,7 @@ MASK_SALU = ("s_and_b64", "s_or_b64", "s_andn2_b64", "s_orn2_b64", "s_xor_b64", 
 
 def assemble(hip, outdir):
     out = os.path.join(outdir, os.path.basename(hip).replace(".hip", ".s"))
-    flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=" + ("off" if hip.endswith("beam.hip") else "on"),
+    flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=" + ("off" if hip.endswith(("beam.hip", "ngram_lm.hip")) else "on"),
              "--cuda-device-only", "-S", hip, "-o", out]
     subprocess.run([HIPCC] + flags, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return out
