@@ -418,6 +418,48 @@ int ms_ctc_greedy_stream_step(const float* x, int rows, int n, int V, int blank,
                               const int32_t* chunk_lens, int32_t* labels, int32_t* label_frames, int cap, int32_t* fresh,
                               void* state, int N, void* stream);
 
+/* ---- post_process/ctc_aligner.py ----------------------------------------- */
+
+/* CTC forced alignment (no counterpart in the reference): the best path of a GIVEN transcript through the scores, i.e. the
+ * Viterbi (max-plus) form of the recursion ms_ctc_loss_forward sums, its back-trace and the frame span of every label.
+ *
+ * Per utterance n: T_n = in_lens[n] rows x[t, n, :] of V scores; a target y_0 .. y_{L-1}, L = tgt_lens[n] (<= L_max), whose
+ * labels start at targets[tgt_offsets[n]] (the padded [N, S] and the concatenated 1-D form alike, as in
+ * ms_ctc_loss_forward) and differ from `blank`; the extended sequence e_s, s = 0 .. S-1, S = 2L+1: e_s = blank for even s,
+ * y_{(s-1)/2} for odd s.
+ * flags = 0 (logits in): lp[t, v] = x[t, n, v] - logsumexp_v x[t, n, :] in float32, by the device's own log-softmax.
+ * flags = MS_CTC_LOG_PROBS_IN: lp[t, v] = x[t, n, v] exactly as given; -inf is allowed and means "impossible".
+ * Recursion in natural-log float32, one rounding per addition and no other arithmetic:
+ *   d_0(0) = lp[0, e_0], d_0(1) = lp[0, e_1] (if S > 1), every other d_0(s) = -inf;
+ *   t >= 1: best = d_{t-1}(s), k = 0;
+ *           if s >= 1 and d_{t-1}(s-1) > best (strictly): best = d_{t-1}(s-1), k = 1;
+ *           if s >= 2, e_s != blank, e_s != e_{s-2} and d_{t-1}(s-2) > best (strictly): best = d_{t-1}(s-2), k = 2;
+ *           d_t(s) = best + lp[t, e_s], back-pointer k -- ties prefer staying, then one step, then the skip;
+ *   end: the final state is S-1 unless S >= 2 and d_{T_n-1}(S-2) > d_{T_n-1}(S-1) strictly; score = d of that state;
+ *        state[t], t = T_n-1 .. 0, by walking the back-pointers.
+ * No alignment: score = -inf when no path exists (T_n < L + #{i: y_i == y_{i-1}}; T_n = 0 with L > 0; impossible symbols);
+ * T_n = 0 with L = 0 gives score 0 and an empty path.  Non-finite input -- a NaN or +inf anywhere in an existing row
+ * (log-probabilities in), a non-finite normaliser of an existing row (logits in) -- gives score = NaN.  In both cases the
+ * utterance has no path: every per-frame output is -1, every span (-1, -1), every token log-probability -inf (NaN when the
+ * score is NaN).  A target label outside [0, V) or equal to `blank`, or tgt_lens[n] outside [0, L_max], is the caller's
+ * error: nothing is read out of bounds for it and the utterance is treated as having no alignment.
+ * Outputs: score [N]; frame_state [N, T] int32 = state[t] for t < T_n, -1 beyond (always fully written);
+ * token_start / token_end [N, L_max] int32 = the first frame with state 2i+1 / one past the last; token_logp [N, L_max] =
+ * the float32 sum of lp[t, y_i] over the token's frames in ascending t; entries i >= L are -1 / -1 / 0 (the three may be
+ * NULL when L_max = 0).
+ * Two launches on `stream` (the normalisers: a wave per frame; the alignment: a workgroup per utterance), no host
+ * synchronisation, no allocation, no bounded spin (hence no status word).  The 2-bit back-pointers of a frame are kept as two
+ * 64-bit planes per 64 states, 16 ceil(S_max / 64) bytes per frame with S_max = 2 L_max + 1: in LDS while T such rows fit
+ * MS_CTC_ALIGN_BP_LDS_BYTES, else in the workspace (ms_ctc_align_workspace_bytes: host arithmetic; 0 for N <= 0; it grows
+ * by N T rows exactly when they leave the LDS).  Supported: T <= 8192, L_max <= 1023, any V; beyond that
+ * MS_ERR_UNSUPPORTED and nothing is launched. */
+#define MS_CTC_ALIGN_BP_LDS_BYTES 98304
+size_t ms_ctc_align_workspace_bytes(int T, int N, int V, int S_max);
+int ms_ctc_align(const float* x, const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_offsets,
+                 const int32_t* tgt_lens, float* score, int32_t* frame_state, int32_t* token_start, int32_t* token_end,
+                 float* token_logp, int T, int N, int V, int L_max, int blank, int flags, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* ---- post_process/ctc_beam_decoder.py ------------------------------------ */
 
 size_t ms_ctc_beam_workspace_bytes(int T, int N, int V, int beam_width);

@@ -86,6 +86,8 @@ SIGNATURES = {
     "ms_ctc_loss_backward_workspace_bytes": (c_size_t, [c_int] * 4),
     "ms_ctc_loss_backward": (c_int, [_P] * 7 + [c_int] * 6 + [_P, c_size_t, _P]),
     "ms_ctc_greedy_decode": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "ms_ctc_align_workspace_bytes": (c_size_t, [c_int] * 4),
+    "ms_ctc_align": (c_int, [_P] * 10 + [c_int] * 6 + [_P, c_size_t, _P]),
     "ms_ctc_greedy_stream_state_bytes": (c_size_t, [c_int]),
     "ms_ctc_greedy_stream_begin": (c_int, [_P, c_int, _P]),
     "ms_ctc_greedy_stream_step": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, c_int, _P]),
