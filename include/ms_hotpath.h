@@ -545,6 +545,29 @@ int ms_ctc_beam_decode_lm(const float* probs, const int32_t* lens, int32_t* out_
                           const void* lm_header_host, size_t lm_table_bytes, int finish, int32_t* beam_len,
                           int32_t* beam_idx, int32_t* beam_plen, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The three entry points above in one, plus the range-safe search and the scored beam.  The arguments of
+ * ms_ctc_beam_decode_rows, then the optional device model of ms_ctc_beam_decode_lm (lm_table = lm_header_host = NULL:
+ * none; with one, lm_factor must be NULL and the workspace is sized by ms_ctc_beam_lm_workspace_bytes, otherwise by
+ * ms_ctc_beam_workspace_bytes), then:
+ *   range_safe != 0: after every frame whose new best beam entry has a stored Pb + Pnb (float32, without the word-count
+ *     factor) below 2^-32, every stored probability of that frame -- the beam's and the frame's candidate tables -- is
+ *     multiplied by 2^-e, e = that sum's unbiased exponent (floor(log2), -126 for a subnormal), and e is added to the
+ *     utterance's int32 scale_log2, kept in the workspace: true value = stored value * 2^scale_log2.  The multiplication
+ *     is exact and the same for every entry, so pruning, model and word factors, the `> 0` test, tie order and every later
+ *     rounding are those of ms_ctc_beam_decode: the transcripts are the same wherever that search stays in float32's normal
+ *     range, and the beam does not run empty where it underflows.  range_safe == 0 runs the kernels of the entry points
+ *     above.  A workspace begun in one mode (t_begin = 0) continues in that mode.
+ *   beam_score [N, beam_width] float32 and scale_log2 [N] int32 (both or neither NULL; they need beam_len / beam_idx /
+ *     beam_plen): the stored Pb + Pnb of beam entries 0 .. beam_len[n] - 1 in beam order and the utterance's scale (0
+ *     with range_safe == 0); ln P(entry) = ln(beam_score) + scale_log2 * ln 2.  Entries past beam_len[n] are not written. */
+int ms_ctc_beam_decode_ex(const float* probs, const int32_t* lens, int32_t* out_idx, int32_t* out_len, int T, int N,
+                          int V, int blank, int beam_width, float prune_threshold, int separator,
+                          const float* word_factor, int t_begin, int t_end, int row0, int rows_held,
+                          const float* lm_factor, int finish, int32_t* beam_len, int32_t* beam_idx, int32_t* beam_plen,
+                          void* workspace, size_t workspace_bytes, void* stream, const void* lm_table,
+                          const void* lm_header_host, size_t lm_table_bytes, int range_safe, float* beam_score,
+                          int32_t* scale_log2);
+
 /* ---- feature front-end: data/preprocess.py + builders/pre_process_step.py ---- */
 
 /* torchaudio.transforms.MFCC as built by builders/pre_process_step.py:33-43 (torchaudio==0.4.0,

@@ -104,6 +104,8 @@ SIGNATURES = {
     "ms_ctc_beam_lm_workspace_bytes": (c_size_t, [c_int] * 5),
     "ms_ctc_beam_decode_lm": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P, c_int, c_int,
                                       c_int, c_int, _P, _P, c_size_t, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "ms_ctc_beam_decode_ex": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P, c_int, c_int,
+                                      c_int, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P, _P, _P, c_size_t, c_int, _P, _P]),
     "ms_rnnt_decode_workspace_bytes": (c_size_t, [c_int] * 10),
     "ms_rnnt_decode": (c_int, [_P, _P, _P, _PP, _PP, _PP, _PP, _P, _P, _P, _P, _P, _P] + [c_int] * 10 + [_P, c_size_t, _P]),
     "ms_mfcc_workspace_bytes": (c_size_t, [c_int] * 5),

@@ -31,6 +31,7 @@
 namespace {
 
 constexpr int HDR_INTS = 16;
+constexpr int HDR_SCALE = 14;      // (RS) scale_log2 of the stored probabilities; [0 .. 2] counters, [4 .. 12] stamps, [13] LM
 enum { F_PRESENT = 1, F_KEPT = 2 };
 constexpr size_t BEAM_LDS_LIMIT = 150 * 1024;
 static_assert(ms_lm::HIST == 4, "a node's word history is stored as one int4");
@@ -104,6 +105,8 @@ struct BeamP {
   int T, N, V, W, blank, sep, t_begin, t_end, finish, stamps;
   float thr;
   BeamLm lm;   // (last: the fields above keep their places in the kernel argument)
+  float* beam_score_out;      // (RS) [N, W] the stored Pb + Pnb of the live beam, beam order
+  int32_t* scale_out;         // (RS) [N] scale_log2: a true value = the stored value * 2^scale_log2
 };
 
 // MS_PIN(x): an empty asm that "modifies" x -- the load that produced x is issued where it is written.  hipcc otherwise sinks an
@@ -147,7 +150,13 @@ __device__ __forceinline__ int find_in_beam(const int* bmn, int W8, int node) {
 // reference's decode size -- 29 symbols (configs/deep_speech_2_en.config), width 8; the arithmetic is untouched.
 // LM: the separator extension's factor comes from the n-gram table in device memory (ngram_lm.h) instead of `lm_factor`.
 // Every addition is under `if constexpr (LM)`; the instantiations without it are what they were.
-template <bool BIG, int NT, int VC = 0, int WC = 0, bool LM = false>
+// RS ("range safe"): once a frame's best stored probability Pb + Pnb falls below 2^-32, every stored probability of that frame
+// is multiplied by the power of two that brings it back into [1, 2) and the exponent goes to the utterance's `scale_log2`
+// (header word HDR_SCALE).  A multiplication by 2^k is exact (k > 0: nothing can round, and nothing comes near overflow),
+// the same factor on every entry changes no comparison, no sort order and no later product's or sum's rounding: the search
+// is the reference's arithmetic with an unbounded exponent, and it does not run empty where float32 underflows.  Every
+// addition is under `if constexpr (RS)`.
+template <bool BIG, int NT, int VC = 0, int WC = 0, bool LM = false, bool RS = false>
 __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int tid = threadIdx.x, n = blockIdx.x;
@@ -217,6 +226,10 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
   for (int k = tid; k < 2 * W8; k += NT) bm_node[k] = -2;     // (members are written below, behind a barrier)
   __syncthreads();
   const int b0 = p.t_begin & 1;      // buffer of the beam / child rows a frame reads = the frame's parity
+  int scale_log2 = 0;                // (RS) the same word in every thread
+  if constexpr (RS) {
+    if (p.t_begin != 0) scale_log2 = hdr[HDR_SCALE];
+  }
   if (p.t_begin == 0) {
     // Pb[-1][()] = 1, Pnb[-1][()] = 0, A_prev = [()]   (ctc_beam_decoder.py:182-192)
     if (tid == 0) {
@@ -527,6 +540,17 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
     __syncthreads();
     MS_BEAM_STAMP(6);
 
+    // (RS) the raw Pb + Pnb of the new beam's first entry: read here, in front of S6's barrier, because behind it S7 rewrites
+    // the word; one word for the whole workgroup, taken into an SGPR so that S7's branch and its barrier are uniform
+    float rs_s0 = 1.0f;
+    if constexpr (RS) {
+      if (Bn > 0) {
+        const int i0 = newbeam[0];
+        rs_s0 = c_pb[cp * M + i0] + c_pnb[cp * M + i0];
+      }
+      rs_s0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rs_s0)));
+    }
+
     // ---- S6: A_prev <- best beam_width candidates; every new beam entry's child row
     for (int idx = tid; idx < Bn * V; idx += NT) {
       const int j = idx == tid ? w_first : idx / V, c = idx == tid ? c_first : idx - (idx / V) * V;
@@ -575,12 +599,26 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
     if (tid == 0) sh[0] = Bn;
     __syncthreads();
     MS_BEAM_STAMP(7);
+
+    // ---- S7 (RS): rescale what the next frame reads -- this frame's tables (through lc_tidx) and the new beam's copies --
+    // by 2^-e, e = the unbiased exponent of rs_s0 (a subnormal's is -126).  The factor is built from the exponent field: no
+    // transcendental, no rounding.  Slots no candidate owns hold stale words; they are multiplied along and never read.
+    if constexpr (RS) {
+      if (rs_s0 < 0x1p-32f) {      // (rs_s0 > 0: a kept candidate's sum; a NaN compares false)
+        const int ef = max((__float_as_int(rs_s0) >> 23) & 0xff, 1);
+        const float mul = __int_as_float((254 - ef) << 23);
+        for (int i = tid; i < M; i += NT) { c_pb[cp * M + i] = c_pb[cp * M + i] * mul; c_pnb[cp * M + i] = c_pnb[cp * M + i] * mul; }
+        for (int w = tid; w < Bn; w += NT) { bm_pb[nb * W + w] = bm_pb[nb * W + w] * mul; bm_pnb[nb * W + w] = bm_pnb[nb * W + w] * mul; }
+        scale_log2 += ef - 127;
+        __syncthreads();
+      }
+    }
   }
 
   // ---- persist state, emit results (the beam and its rows sit in the buffers of the frame the loop stopped at)
   const int eb = t & 1;
   const int B = sh[0];
-  if (tid == 0) { hdr[0] = sh[2]; hdr[1] = sh[3]; hdr[2] = B; if constexpr (LM) hdr[13] = sh[4]; }
+  if (tid == 0) { hdr[0] = sh[2]; hdr[1] = sh[3]; hdr[2] = B; if constexpr (LM) hdr[13] = sh[4]; if constexpr (RS) hdr[HDR_SCALE] = scale_log2; }
   if (stamping)
     for (int k = 0; k < 9; ++k) hdr[4 + k] = (int)st_acc[k];
   for (int i = tid; i < M; i += NT) { tbl_pb[i] = c_pb[(eb ^ 1) * M + i]; tbl_pnb[i] = c_pnb[(eb ^ 1) * M + i]; }
@@ -607,6 +645,24 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamP p) {
       for (int i = L - 1; i >= 0; --i) { p.beam_idx_out[((size_t)n * W + w) * p.T + i] = node_sym[nd]; nd = node_parent[nd]; }
     }
   }
+  if constexpr (RS) {
+    if (p.beam_score_out != nullptr) {
+      if (tid == 0) p.scale_out[n] = scale_log2;
+      for (int w = tid; w < B; w += NT) p.beam_score_out[(size_t)n * W + w] = bm_pb[eb * W + w] + bm_pnb[eb * W + w];
+    }
+  }
+}
+
+// The same read-out for a search run by the kernels without RS (ms_ctc_beam_decode_ex, range_safe = 0): the beam's stored
+// probabilities are in the workspace in beam order, scale_log2 is 0
+__global__ void beam_score_kernel(const char* ws, size_t per_utt, size_t hdr_off, size_t pb_off, size_t pnb_off, int W,
+                                  float* beam_score, int32_t* scale_out) {
+  const char* u = ws + (size_t)blockIdx.x * per_utt;
+  const int B = reinterpret_cast<const int*>(u + hdr_off)[2];
+  const float* pb = reinterpret_cast<const float*>(u + pb_off);
+  const float* pnb = reinterpret_cast<const float*>(u + pnb_off);
+  if (threadIdx.x == 0) scale_out[blockIdx.x] = 0;
+  for (int w = threadIdx.x; w < B && w < W; w += blockDim.x) beam_score[(size_t)blockIdx.x * W + w] = pb[w] + pnb[w];
 }
 
 }  // namespace
@@ -621,7 +677,8 @@ static int beam_decode_window(const float* probs, const int32_t* lens, int32_t* 
                               int blank, int beam_width, float prune_threshold, int separator, const float* word_factor,
                               int t_begin, int t_end, int row0, int rows_held, const float* lm_factor, int finish,
                               int32_t* beam_len, int32_t* beam_idx, int32_t* beam_plen, void* workspace, size_t workspace_bytes,
-                              void* stream, const ms_lm::Tab* lm_tab = nullptr) {
+                              void* stream, const ms_lm::Tab* lm_tab = nullptr, int range_safe = 0, float* beam_score = nullptr,
+                              int32_t* scale_log2 = nullptr) {
   MS_REQUIRE(probs && lens && workspace, "null pointer");
   MS_REQUIRE(T > 0 && N > 0 && V > 0 && beam_width > 0, "bad shape");
   MS_REQUIRE(blank >= 0 && blank < V, "blank out of range");
@@ -639,6 +696,8 @@ static int beam_decode_window(const float* probs, const int32_t* lens, int32_t* 
     return MS_ERR_WORKSPACE;
   }
   MS_REQUIRE(beam_width <= 256, "beam_width must not exceed 256");
+  MS_REQUIRE((beam_score == nullptr) == (scale_log2 == nullptr), "beam_score/scale_log2 go together");
+  MS_REQUIRE(beam_score == nullptr || beam_idx != nullptr, "beam_score goes with beam_len/beam_idx/beam_plen");
   const size_t lds = L.big ? 0 : beam_lds_bytes(V, beam_width) + (lm_tab ? (size_t)2 * beam_width * 4 : 0);
   static ms::DeviceOnce attr_once;
   if (attr_once.need()) {
@@ -663,6 +722,29 @@ static int beam_decode_window(const float* probs, const int32_t* lens, int32_t* 
   {
     const char* e = getenv("MS_BEAM_STAMPS");
     p.stamps = (e && e[0] == '1') ? 1 : 0;
+  }
+  p.beam_score_out = beam_score; p.scale_out = scale_log2;
+  if (range_safe) {      // the RS twins: the BIG path, 29 x 8, the generic kernel, each with and without the device model
+    static ms::DeviceOnce rs_once;
+    if (rs_once.need()) {
+      MS_HIP(hipFuncSetAttribute((const void*)beam_kernel<false, 256, 0, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MS_HIP(hipFuncSetAttribute((const void*)beam_kernel<false, 256, 0, 0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      rs_once.done();
+    }
+    const bool cs = V == 29 && beam_width == 8 && !(getenv("MS_BEAM_CONST") && getenv("MS_BEAM_CONST")[0] == '0');
+    if (lm_tab) {
+      p.lm.tab = *lm_tab;
+      p.lm_factor = nullptr;
+      if (L.big) hipLaunchKernelGGL((beam_kernel<true, 256, 0, 0, true, true>), dim3(N), dim3(256), 0, (hipStream_t)stream, p);
+      else if (cs) hipLaunchKernelGGL((beam_kernel<false, 256, 29, 8, true, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+      else hipLaunchKernelGGL((beam_kernel<false, 256, 0, 0, true, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+    } else {
+      if (L.big) hipLaunchKernelGGL((beam_kernel<true, 256, 0, 0, false, true>), dim3(N), dim3(256), 0, (hipStream_t)stream, p);
+      else if (cs) hipLaunchKernelGGL((beam_kernel<false, 256, 29, 8, false, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+      else hipLaunchKernelGGL((beam_kernel<false, 256, 0, 0, false, true>), dim3(N), dim3(256), lds, (hipStream_t)stream, p);
+    }
+    MS_LAUNCH_CHECK();
+    return MS_OK;
   }
   static const int nt_env = getenv("MS_BEAM_THREADS") ? atoi(getenv("MS_BEAM_THREADS")) : 0;      // A/B switch: 64 or 256
   const bool one_wave = nt_env == 64;
@@ -737,4 +819,34 @@ extern "C" int ms_ctc_beam_decode_lm(const float* probs, const int32_t* lens, in
   return beam_decode_window(probs, lens, out_idx, out_len, T, N, V, blank, beam_width, prune_threshold, separator, word_factor,
                             t_begin, t_end, row0, rows_held, nullptr, finish, beam_len, beam_idx, beam_plen, workspace,
                             workspace_bytes, stream, &tab);
+}
+
+// ---- every option of the three entry points above in one, plus the range-safe search and the scored beam
+extern "C" int ms_ctc_beam_decode_ex(const float* probs, const int32_t* lens, int32_t* out_idx, int32_t* out_len, int T, int N,
+                                     int V, int blank, int beam_width, float prune_threshold, int separator,
+                                     const float* word_factor, int t_begin, int t_end, int row0, int rows_held,
+                                     const float* lm_factor, int finish, int32_t* beam_len, int32_t* beam_idx,
+                                     int32_t* beam_plen, void* workspace, size_t workspace_bytes, void* stream,
+                                     const void* lm_table, const void* lm_header_host, size_t lm_table_bytes, int range_safe,
+                                     float* beam_score, int32_t* scale_log2) {
+  MS_REQUIRE((lm_table == nullptr) == (lm_header_host == nullptr), "lm_table/lm_header_host go together");
+  MS_REQUIRE(lm_table == nullptr || lm_factor == nullptr, "lm_factor and a device language model exclude each other");
+  ms_lm::Tab tab{};
+  if (lm_table != nullptr) {
+    MS_REQUIRE(separator >= 0, "a language model needs a separator");
+    const char* bad = ms_lm::header_problem(lm_header_host, lm_table_bytes);
+    MS_REQUIRE(bad == nullptr, bad ? bad : "");
+    tab = ms_lm::make_tab(lm_header_host, lm_table);
+  }
+  const int rc = beam_decode_window(probs, lens, out_idx, out_len, T, N, V, blank, beam_width, prune_threshold, separator,
+                                    word_factor, t_begin, t_end, row0, rows_held, lm_factor, finish, beam_len, beam_idx,
+                                    beam_plen, workspace, workspace_bytes, stream, lm_table ? &tab : nullptr,
+                                    range_safe ? 1 : 0, beam_score, scale_log2);
+  if (rc != MS_OK || range_safe || beam_score == nullptr) return rc;
+  BeamLm lm_state{};
+  const BeamLayout L = beam_layout(T, V, beam_width, lm_table ? &lm_state : nullptr);
+  hipLaunchKernelGGL(beam_score_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, (const char*)workspace, L.per_utt, L.hdr,
+                     L.beam_pb, L.beam_pnb, beam_width, beam_score, scale_log2);
+  MS_LAUNCH_CHECK();
+  return MS_OK;
 }

@@ -14,6 +14,8 @@ between pushes and end with exactly the transcript the whole-clip decoder gives:
   current best prefix and may change as audio arrives.  A host ``language_model`` is refused: the callback stays with
   ``CTCBeamDecoder``.  An ``NGramLanguageModel`` is taken: its table is in device memory and every prefix's model state
   in the workspace, so ``ms_ctc_beam_decode_lm`` advances over a push exactly as the model-free search does.
+  ``range_safe=True`` is ``CTCBeamDecoder``'s: the search with an unbounded exponent (``ms_ctc_beam_decode_ex``), its scale
+  carried in the workspace from push to push; ``nbest()`` is the scored beam beside ``best()``.
 """
 import ctypes
 from typing import List, Optional
@@ -23,6 +25,7 @@ import torch
 from myrtlespeech_amd import _lib
 from myrtlespeech_amd.language_model import NGramLanguageModel
 from myrtlespeech_amd.post_process._common import SUPPORTED_LENGTH_DTYPES, check_decoder_args, ragged_to_lists
+from myrtlespeech_amd.post_process.ctc_beam_decoder import BeamHypothesis, read_nbest
 
 # layout of ms_ctc_greedy_stream_step's state (include/ms_hotpath.h): int32 words, a header and four words per stream
 _HDR_INTS, _STREAM_INTS = 16, 4
@@ -148,7 +151,10 @@ class StreamingCTCBeamDecoder:
     """Prefix beam search (ctc_beam_decoder.py:175-258) of a batch of streams, advanced over the rows of each push."""
 
     def __init__(self, blank_index: int, beam_width: int, prune_threshold: float = 0.001,
-                 separator_index: Optional[int] = None, word_weight: float = 1.0, language_model=None, lm_weight=None):
+                 separator_index: Optional[int] = None, word_weight: float = 1.0, language_model=None, lm_weight=None,
+                 range_safe: bool = False):
+        if not isinstance(range_safe, bool):
+            raise ValueError(f"range_safe={range_safe!r} must be a bool")
         if blank_index < 0:
             raise ValueError(f"blank_index={blank_index} must be >= 0")
         if beam_width <= 0:
@@ -174,6 +180,7 @@ class StreamingCTCBeamDecoder:
         # as in the reference, a model without a separator is never consulted
         self.language_model = language_model if separator_index is not None else None
         self.lm_weight = lm_weight
+        self.range_safe = range_safe
         self._lens = None
 
     def begin(self, lens: torch.Tensor, total_frames: int) -> None:
@@ -203,8 +210,22 @@ class StreamingCTCBeamDecoder:
         if self._lens is None:
             raise RuntimeError("call begin(lens, total_frames) first")
 
-    def _call(self, window, t0, t1, row0, finish):
+    def _call(self, window, t0, t1, row0, finish, beam=None):
+        """``beam``: (beam_len, beam_idx, beam_plen, beam_score, scale_log2) for the scored read-out."""
         sep = -1 if self.separator_index is None else int(self.separator_index)
+        if self.range_safe or beam is not None:
+            table = blob = None
+            if self.language_model is not None:
+                table, blob = self.language_model.device_table(self.lm_weight)
+            b = beam if beam is not None else (None,) * 5
+            _lib.check(_lib.load().ms_ctc_beam_decode_ex(
+                _lib.ptr(window), _lib.ptr(self._lens), _lib.ptr(self._out_idx), _lib.ptr(self._out_len), self._total,
+                self._n, self._symbols, self.blank_index, self.beam_width, float(self.prune_threshold), sep,
+                _lib.ptr(self._wf), t0, t1, row0, window.shape[0], None, finish, _lib.ptr(b[0]), _lib.ptr(b[1]),
+                _lib.ptr(b[2]), _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr(), _lib.ptr(table),
+                ctypes.c_void_p(blob.ctypes.data if blob is not None else 0), blob.size if blob is not None else 0,
+                1 if self.range_safe else 0, _lib.ptr(b[3]), _lib.ptr(b[4])), "ms_ctc_beam_decode_ex")
+            return
         if self.language_model is not None:
             table, blob = self.language_model.device_table(self.lm_weight)
             _lib.check(_lib.load().ms_ctc_beam_decode_lm(
@@ -255,6 +276,25 @@ class StreamingCTCBeamDecoder:
         # a read-out: no frame is processed (t_begin == t_end), the last window (it ends at row _t) is not read
         self._call(self._window, self._t, self._t, self._t - self._window.shape[0], 1)
         return ragged_to_lists(self._out_idx, self._out_len)
+
+    def nbest(self, n: Optional[int] = None) -> List[List[BeamHypothesis]]:
+        """The beam of every stream after the rows pushed so far, best first, at most ``min(n, beam_width)`` hypotheses
+        each (``CTCBeamDecoder.decode_nbest``)."""
+        self._started()
+        if n is None:
+            n = self.beam_width
+        if isinstance(n, bool) or not isinstance(n, int) or n <= 0:
+            raise ValueError(f"n={n!r} must be an int > 0")
+        if self._symbols is None:      # no row yet: the empty prefix with probability 1
+            return [[BeamHypothesis([], 0.0)] for _ in range(self._n)]
+        w = self.beam_width
+        beam = (torch.empty(self._n, dtype=torch.int32, device="cuda"),
+                torch.empty((self._n, w, self._total), dtype=torch.int32, device="cuda"),
+                torch.empty((self._n, w), dtype=torch.int32, device="cuda"),
+                torch.empty((self._n, w), dtype=torch.float32, device="cuda"),
+                torch.empty(self._n, dtype=torch.int32, device="cuda"))
+        self._call(self._window, self._t, self._t, self._t - self._window.shape[0], 1, beam)
+        return read_nbest(*beam, n)
 
     def result(self) -> List[List[int]]:
         """The transcripts: ``best()`` once every row has been pushed."""
