@@ -650,6 +650,59 @@ int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const float* embeddi
                    int N, int V, int D, int H, int L, int J, int beam_width, int max_symbols, int greedy, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- RNN-T (transducer) loss: forward, and the gradient with respect to the joint's logits.  OWN specification, like
+ *      everything under the RNN-T label (the reference snapshot has no transducer; parity unpinned); restated in numpy by
+ *      tests/rnnt_loss_ref.py.  Graves 2012, "Sequence Transduction with Recurrent Neural Networks", section 2.4.
+ *
+ * Inputs.  logits [N, T, U1, V1] float32, contiguous: joint-network outputs, not necessarily normalised.  U1 = U_max + 1,
+ * V1 = number of symbols, blank any index in [0, V1).  Per utterance n: T_n = in_lens[n] in [1, T], U_n = tgt_lens[n] in
+ * [0, U1 - 1]; labels y_0 .. y_{U_n - 1} = targets[n (U1 - 1) + u] (padded, int32), each in [0, V1) and != blank.  targets
+ * may be NULL when U1 == 1.  All indexing is size_t (N T U1 V1 passes 2^31 at realistic sizes).
+ *
+ * Recursion, for the EXISTING cells t < T_n, u <= U_n, in natural-log float32:
+ *   Z(t,u)     = logsumexp_v logits[n,t,u,:]   (max-subtracted)
+ *   lp(t,u,v)  = logits[n,t,u,v] - Z(t,u);   b(t,u) = lp(t,u,blank);   e(t,u) = lp(t,u,y_u) for u < U_n
+ *   alpha(0,0) = 0
+ *   alpha(t,u) = logaddexp(alpha(t-1,u) + b(t-1,u), alpha(t,u-1) + e(t,u-1))     (a term whose predecessor lies outside the
+ *                                                                                 lattice is absent)
+ *   ll         = alpha(T_n-1, U_n) + b(T_n-1, U_n);   nll[n] = -ll
+ *   beta(T_n-1, U_n) = b(T_n-1, U_n)
+ *   beta(t,u)  = logaddexp(beta(t+1,u) + b(t,u), beta(t,u+1) + e(t,u))
+ *   logaddexp(-inf, -inf) = -inf, never NaN; a -inf logit is allowed and means "impossible".
+ *
+ * Gradient of sum_n grad_nll[n] nll[n] with respect to the logits (log-softmax included), for an existing cell:
+ *   grad[n,t,u,v] = grad_nll[n] ( exp(lp(t,u,v) + alpha(t,u) + beta(t,u) - ll)
+ *                                 - [v == blank] exp(alpha(t,u) + b(t,u) + beta(t+1,u) - ll)
+ *                                 - [u < U_n and v == y_u] exp(alpha(t,u) + e(t,u) + beta(t,u+1) - ll) )
+ *   at (T_n-1, U_n) the blank term is exp(alpha + b - ll); for every other (T_n-1, u) it is 0.
+ *   grad is always fully written: every element of a cell that does not exist is 0.
+ *
+ * Edge cases.
+ *   ll = -inf (the transcript is impossible under the given -inf's): nll = +inf, the utterance's gradient all 0.
+ *   a non-finite Z in an existing cell (a NaN or +inf logit, a row of -inf only): nll = NaN, the gradient NaN in the
+ *     utterance's existing cells and 0 outside them.
+ *   what lies in cells that do not exist (NaN included) and in targets past U_n changes no output bit.
+ *   T_n outside [1, T], U_n outside [0, U1 - 1], a label outside [0, V1) or equal to blank: the caller's error; nothing is read
+ *     out of bounds for it; nll = +inf and a zero gradient.
+ *
+ * Memory.  lattice is caller-owned float32 [3][N][T][U1] = Z, alpha, beta (ms_rnnt_loss_lattice_bytes = 12 N T U1); only its
+ * existing cells are defined.  The forward writes it, the backward reads it (an autograd node saves it): the workspace is
+ * transient and nothing is kept between the calls.  ms_rnnt_loss_workspace_bytes = 2 planes of N (T + U1 - 1) U1 floats,
+ * each rounded up to 256 bytes: b and e, gathered by the normaliser pass and stored skewed by anti-diagonal, [n][t + u][u].
+ * Both size queries are host arithmetic and return 0 for non-positive shapes.
+ * Supported: U1 <= 1024, any T, any V1 >= 1 (and N T U1 < 2^33 cells); MS_ERR_UNSUPPORTED beyond, nothing launched.
+ * Neither call synchronises the host or allocates.  Three passes -- normalisers (forward), lattice (forward; 2 N workgroups,
+ * alpha and beta side by side), gradient (backward); no kernel waits on another workgroup, so there is no bounded spin and
+ * no status word.  Results are deterministic: the same inputs give the same bits. */
+size_t ms_rnnt_loss_lattice_bytes(int N, int T, int U1);
+size_t ms_rnnt_loss_workspace_bytes(int N, int T, int U1, int V1);
+int ms_rnnt_loss_forward(const float* logits, const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens,
+                         float* nll, float* lattice, int N, int T, int U1, int V1, int blank, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int ms_rnnt_loss_backward(const float* logits, const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens,
+                          const float* nll, const float* lattice, const float* grad_nll, float* grad, int N, int T, int U1,
+                          int V1, int blank, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,1 +1,1 @@
-"""CTC loss."""
+"""CTC loss (``loss.ctc_loss.CTCLoss``) and transducer loss (``loss.rnnt_loss.RNNTLoss``)."""

@@ -1,0 +1,134 @@
+"""Transducer (RNN-T) loss -- this repository's OWN specification (the reference snapshot has no transducer, see
+model/rnnt.py; parity unpinned).  The specification is the comment on ``ms_rnnt_loss_forward`` in include/ms_hotpath.h
+(Graves 2012, section 2.4); tests/rnnt_loss_ref.py restates it in numpy.
+
+``RNNTLoss(blank, reduction)`` is called like ``CTCLoss``: ``loss((logits[N, T, U + 1, V + 1], logit_lens), (y[N, U], y_lens))``
+with the joint network's outputs (normalised or not: the loss applies its own log-softmax over the symbols) and returns
+``nll[N] = -log P(y_n | logits_n)`` (``none``), its sum (``sum``) or the sum divided by the batch size N (``mean`` -- NOT the
+CTC wrapper's mean over per-target-length-normalised losses).  The reduction is done with torch ops.  When the logits
+require grad the loss is an autograd node whose backward is ``ms_rnnt_loss_backward``; the node saves the lattice (Z, alpha,
+beta) the forward wrote, the module itself keeps no state and the workspace is transient.
+
+With ``RNNT.joint_lattice`` the ``none`` reduction scores a transcript under a model.
+"""
+from typing import Tuple
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from myrtlespeech_amd import _lib
+
+_REDUCTIONS = ("none", "sum", "mean")
+MAX_U1 = 1024       # the lattice pass runs one thread per u in one workgroup
+
+
+class _RNNTLossFunction(torch.autograd.Function):
+    """Forward = ``ms_rnnt_loss_forward`` (nll per utterance); backward = ``ms_rnnt_loss_backward`` (logits gradient only)."""
+
+    @staticmethod
+    def forward(ctx, x, run_forward, meta):
+        nll, lattice = run_forward(x)
+        ctx.save_for_backward(x, nll, lattice)
+        ctx.meta = meta
+        return nll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, nll, lattice = ctx.saved_tensors
+        m = ctx.meta
+        n, t, u1, v1 = x.shape
+        grad_nll = _lib.f32c(grad_out).reshape(n).contiguous()
+        grad = torch.empty_like(x)
+        _lib.check(_lib.load().ms_rnnt_loss_backward(_lib.ptr(x), _lib.ptr(m["xl_dev"]), _lib.ptr(m["y_dev"]),
+                                                     _lib.ptr(m["yl_dev"]), _lib.ptr(nll), _lib.ptr(lattice),
+                                                     _lib.ptr(grad_nll), _lib.ptr(grad), n, t, u1, v1, m["blank"],
+                                                     _lib.stream_ptr()), "ms_rnnt_loss_backward")
+        return grad, None, None
+
+
+def _int_lens(lens: torch.Tensor, what: str) -> torch.Tensor:
+    if not isinstance(lens, torch.Tensor) or lens.is_floating_point() or lens.is_complex() or lens.dtype == torch.bool:
+        raise ValueError(f"{what} must be an integer tensor")
+    return lens.detach().reshape(-1).to("cpu", torch.int64)
+
+
+class RNNTLoss(torch.nn.Module):
+    def __init__(self, blank: int, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in _REDUCTIONS:
+            raise ValueError(f"{reduction} is not a valid value for reduction")
+        if int(blank) < 0:
+            raise ValueError(f"blank={blank} must be >= 0")
+        self.blank = int(blank)
+        self.reduction = reduction
+
+    def extra_repr(self) -> str:
+        return f"blank={self.blank}, reduction={self.reduction}"
+
+    def forward(self, inputs: Tuple[torch.Tensor, torch.Tensor], targets: Tuple[torch.Tensor, torch.Tensor]
+                ) -> torch.Tensor:
+        x, x_lens = inputs
+        y, y_lens = targets
+        # ---- validation: ValueError before a device is needed
+        if x.dim() != 4:
+            raise ValueError("logits must be [batch, max_seq_len, max_target_len + 1, symbols]")
+        n, t, u1, v1 = x.shape
+        if min(n, t, u1, v1) <= 0:
+            raise ValueError(f"logits of shape {tuple(x.shape)} have an empty dimension")
+        if u1 > MAX_U1:
+            raise ValueError(f"max_target_len + 1 = {u1} exceeds the supported {MAX_U1}")
+        if not 0 <= self.blank < v1:
+            raise ValueError(f"blank={self.blank} must be in [0, {v1})")
+        if y.dim() != 2 or y.shape[0] != n:
+            raise ValueError(f"targets must be [batch = {n}, max_target_len], got {tuple(y.shape)}")
+        if y.shape[1] != u1 - 1:
+            raise ValueError(f"targets are padded to {y.shape[1]} labels, the logits hold {u1 - 1} + 1 rows per frame")
+        if y.is_floating_point():
+            raise ValueError("targets must be an integer tensor")
+        xl, yl = _int_lens(x_lens, "logit lengths"), _int_lens(y_lens, "target lengths")
+        if xl.numel() != n or yl.numel() != n:
+            raise ValueError(f"lengths of batch {xl.numel()} / {yl.numel()} != logits batch {n}")
+        if int(xl.min()) < 1 or int(xl.max()) > t:
+            raise ValueError(f"logit lengths must be in [1, {t}]")
+        if int(yl.min()) < 0 or int(yl.max()) > u1 - 1:
+            raise ValueError(f"target lengths must be in [0, {u1 - 1}]")
+        # (a label outside [0, V1) or equal to the blank is not looked for here -- the targets may live on the device; the
+        # kernels index nothing with it and give that utterance nll = +inf and a zero gradient)
+        _lib.require_gpu()
+        lib = _lib.load()
+        x = _lib.f32c(x)
+        # ONE staged upload for what starts on the host (ctc_loss.py)
+        host_parts = [xl.to(torch.int32), yl.to(torch.int32)]
+        y_on_host = not y.is_cuda
+        if y_on_host and y.numel():
+            host_parts.append(y.detach().to(torch.int32).reshape(-1))
+        packed = _lib.upload(torch.cat(host_parts))
+        xl_dev, yl_dev = packed[:n], packed[n:2 * n]
+        if not y.numel():
+            y_dev = None                                   # U1 == 1: the ABI takes NULL
+        elif y_on_host:
+            y_dev = packed[2 * n:]
+        else:
+            y_dev = y.detach().to(dtype=torch.int32).contiguous().reshape(-1)
+        blank = self.blank
+
+        def run_forward(logits: torch.Tensor):
+            nll = torch.empty(n, dtype=torch.float32, device="cuda")
+            lattice = torch.empty(lib.ms_rnnt_loss_lattice_bytes(n, t, u1) // 4, dtype=torch.float32, device="cuda")
+            nbytes = lib.ms_rnnt_loss_workspace_bytes(n, t, u1, v1)
+            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device="cuda")     # transient: nothing outlives the call
+            _lib.check(lib.ms_rnnt_loss_forward(_lib.ptr(logits), _lib.ptr(xl_dev), _lib.ptr(y_dev), _lib.ptr(yl_dev),
+                                                _lib.ptr(nll), _lib.ptr(lattice), n, t, u1, v1, blank, _lib.ptr(ws),
+                                                ws.numel(), _lib.stream_ptr()), "ms_rnnt_loss_forward")
+            return nll, lattice
+
+        if torch.is_grad_enabled() and x.requires_grad:
+            meta = dict(blank=blank, xl_dev=xl_dev, yl_dev=yl_dev, y_dev=y_dev)
+            nll = _RNNTLossFunction.apply(x, run_forward, meta)
+        else:
+            nll = run_forward(x)[0]
+        if self.reduction == "none":
+            return nll
+        total = nll.sum()
+        return total if self.reduction == "sum" else total / n

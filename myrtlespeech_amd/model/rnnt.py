@@ -100,3 +100,34 @@ class RNNT(torch.nn.Module):
     def encode(self, x: Tuple[torch.Tensor, torch.Tensor], hx: Optional[object] = None):
         (enc, lens), _ = self.encoder(x, hx)
         return enc, lens
+
+    def joint_lattice(self, enc: torch.Tensor, lens: torch.Tensor, targets: torch.Tensor, target_lens: torch.Tensor
+                      ) -> torch.Tensor:
+        """The joint's log-probabilities for GIVEN transcripts: enc [T, N, E] encoder frames, targets [N, U] padded labels ->
+        [N, T, U + 1, V + 1], row (n, t, u) = log P(symbol | frame t, y_n[:u]) -- what ``loss.rnnt_loss.RNNTLoss`` takes, so
+        ``RNNTLoss(blank=V, reduction="none")((lattice, lens), (targets, target_lens))`` is -log P(transcript | audio).
+        Built from the decoders' pieces only (``predictor.step`` over blank and then the labels, ``joint.project_encoder``,
+        ``joint.logprobs``) and detached: it serves scoring, not training.  The predictor is causal, so what the padding of
+        ``targets`` holds (the embedding look-up clamps it) only reaches rows u > target_lens[n], which the loss never reads;
+        ``lens`` / ``target_lens`` are checked against the shapes and otherwise left to the loss."""
+        _lib.require_gpu()
+        if enc.dim() != 3 or targets.dim() != 2 or targets.shape[0] != enc.shape[1]:
+            raise ValueError(f"enc must be [T, N, E] and targets [N, U], got {tuple(enc.shape)} and {tuple(targets.shape)}")
+        t, n, _ = enc.shape
+        u_max = targets.shape[1]
+        if lens.numel() != n or target_lens.numel() != n:
+            raise ValueError(f"lengths of batch {lens.numel()} / {target_lens.numel()} != encoder batch {n}")
+        with torch.no_grad():
+            enc_p = self.joint.project_encoder(enc.detach())                    # [T*N, J], row t*N + n
+            y = targets.detach().to(device="cuda", dtype=torch.int32)
+            labels = torch.full((n,), self.predictor.blank, dtype=torch.int32, device="cuda")
+            state = self.predictor.zero_state(n)
+            enc_rows = torch.arange(t * n, dtype=torch.int32, device="cuda")
+            out = torch.empty((n, t, u_max + 1, self.joint.vocab_size + 1), dtype=torch.float32, device="cuda")
+            for u in range(u_max + 1):
+                pred, state = self.predictor.step(labels, state)                # [N, H]: the prediction after y[:u]
+                logp = self.joint.logprobs(enc_p, enc_rows, pred.repeat(t, 1))  # row t*N + n pairs frame t with utterance n
+                out[:, :, u, :] = logp.reshape(t, n, -1).transpose(0, 1)
+                if u < u_max:
+                    labels = y[:, u].contiguous()
+        return out
