@@ -2,32 +2,45 @@
 // snapshot has no transducer; the specification is this repository's own
 // (myrtlespeech_amd/model/rnnt.py, oracle/rnnt_oracle.py).
 //
-// The whole decode of a batch is ONE host call that enqueues a fixed launch sequence per frame and never reads anything
-// back: hypothesis lists, the prefix trie, the predictor-state pool and the emission lists all live in the caller's
-// workspace.  Per frame and emission round:
-//   joint_slots_kernel   log P(. | frame t, hypothesis) for every live hypothesis row (one workgroup per row); a row whose
-//                        predictor output is fresh adds the pred_proj GEMM's K-slice partial sums itself and commits them
-//   beam_round_kernel    per utterance: blank transitions merge into the next frame's set B (same prefix = same trie node,
-//                        float32 scores joined by logaddexp), the beam_width best label extensions become the live set
-//   greedy_round_kernel  per utterance: argmax; blank ends the frame, a label is emitted
-//   predictor step       gather [embedding(label) | h_src] rows -> exact-f32 MFMA GEMM against [W_ih | W_hh] ->
-//                        lstm_cell_kernel (writes the new state, builds the next layer's rows) -> ... -> pred_proj GEMM
-//   beam_frame_end_kernel  B sorted (stable, descending) -> beam_width survivors; their states move to the frame-start region
-// Rows of utterances that have ended (t >= len) or of empty beam slots are skipped inside the kernels, so the beam's launch
-// sequence does not depend on the data.
+// The whole decode of a batch is ONE host call that enqueues launches and never reads a hypothesis back: hypothesis lists, the
+// prefix trie, the predictor-state pool and the emission lists all live in the caller's workspace.  Rows of utterances that have
+// ended (t >= len) or of empty beam slots are skipped inside the kernels, so the beam's launch sequence does not depend on the
+// data.  Three launch sequences share the file:
 //
-// Greedy decode (round 3) does not pay for blanks any more.  The predictor's output only changes when a label is emitted, so
-// between two emissions of an utterance every frame's joint is evaluated against the SAME predictor output: one iteration =
+// Beam, the re-cut sequence (beam2_*; H % 64 == 0, J % 32 == 0 and the LDS conditions at its gate in ms_rnnt_decode; described
+// in full above pack_rows3_kernel).  Per frame and emission round:
+//   beam2_joint_kernel / beam2_joint_g_kernel   pred_proj + joint of 32 or 64 hypothesis rows x 32 joint units; after a predictor
+//                                               step the same launch computes G = W_hh . h of the step's new states
+//   beam2_round_kernel                          per utterance: log-softmax, blank merge into B, the beam_width best extensions
+//   beam2_cell0_kernel, pred_gemm3_cell_g_kernel  the predictor step of the picked extensions
+//   beam2_frame_end_kernel                      the frame's last round and the beam_width survivors of B, their states moved
+//
+// Beam, the round-4 sequence (every other shape).  Per frame and emission round:
+//   joint_slots_kernel     log P(. | frame t, hypothesis) for every live hypothesis row (one workgroup per row); a row whose
+//                          predictor output is fresh adds the pred_proj GEMM's K-slice partial sums itself and commits them
+//   beam_round_kernel      per utterance: blank transitions merge into the next frame's set B (same prefix = same trie node,
+//                          float32 scores joined by logaddexp), the beam_width best label extensions become the live set
+//   predictor_step()       pred_gather_kernel builds the rows [embedding(label) | h_src]; then per layer either ONE launch
+//                          (pred_layer_fused_kernel: split-operand gate GEMM + cell, when every layer has K % 128 == 0 and
+//                          H % 16 == 0) or the exact-f32 GEMM in KSPLIT K slices + lstm_cell_kernel; then the pred_proj GEMM
+//   beam_frame_end_kernel  B sorted (stable, descending) -> beam_width survivors; their states move to the frame-start region
+// Both beam sequences apply the same list rules through the same device functions (beam_blank_merge, beam_extend, beam_select):
+// first arrival keeps its state, ties go to the lowest flat index, the first maximum wins among equals.
+//
+// Greedy does not pay for blanks.  The predictor's output only changes when a label is emitted, so between two emissions of an
+// utterance every frame's joint is evaluated against the SAME predictor output: one iteration =
 //   joint_slots_kernel<CHUNK>  log P(. | frame cur_t[i] + c, pred_i) for GREEDY_CHUNK consecutive frames of every utterance at once
 //   greedy_scan_kernel         per utterance: walk those frames in order, blanks advance the frame, the FIRST label is emitted
 //                              (at most max_symbols per frame, then the frame advances), requests ONE predictor step and stops
-//   predictor step             only for the utterances that emitted
+//   predictor_step()           only for the utterances that emitted
 // i.e. about (labels of the longest transcript + blank runs longer than a chunk) iterations instead of T x max_symbols rounds,
 // with the same arithmetic per (frame, prediction) pair and therefore the same transcripts.  The number of iterations depends
 // on the data: the host enqueues iterations ahead and every few of them fetches a device counter of finished utterances
 // (4 bytes, asynchronously, looked at two checks later so that the queue never drains).
 #include <math.h>
 #include <stdlib.h>
+
+#include <utility>
 
 #include "common.h"
 
@@ -110,7 +123,7 @@ DecLayout dec_layout(int T, int N, int V, int D, int H, int L, int J, int w, int
   }
   W.wcat = take(wc * 6);      // float32 rows [4H][K] (4 B per weight) or three bf16 planes of them (6 B): sized for the planes
   W.bcat = take(bc * 4);
-  // ---- the round-5 beam path (beam2_*): see the comment above pred_gemm3_kernel
+  // ---- the re-cut beam sequence (beam2_*): see the comment above pack_rows3_kernel
   if (!greedy) {
     const size_t rpad = (size_t)((R + 63) / 64 * 64);
     W.v2_E = take((size_t)V1 * 4 * H * 4);
@@ -154,23 +167,15 @@ __global__ void pack_cat_kernel(const float* __restrict__ w_ih, const float* __r
 }
 
 
-// ---- the predictor's gate GEMMs as an error-free bf16 split (round 4).  gates[R <= 128.., 4H] = x[R, K] . Wcat[4H, K]^T with
-// R = utterances x beam width hypothesis rows (128 at configs[3]) ran as exact-f32 MFMA in 128 x 32 tiles and eight K slices:
-// 17.6 us per launch, four launches per frame, 45 % of the decode (profiles/r04e_cfg4_kernel_stats.csv) -- float32 MFMA issues
-// 1/16 of the bf16 rate.  Here every float32 operand is written as THREE bf16 values h + m + l (8 + 8 + 8 significand bits: an
-// exact decomposition) and the product keeps the six terms down to 2^-24 relative (hh, hm, mh, mm, hl, lh), accumulated in float32:
-// float32-grade products at 6/16 of the float32 MFMA time.  The weights are split once per decode call (pack_cat3_kernel), the
-// rows by the kernels that produce them (pred_gather_kernel, lstm_cell_kernel: store_split3), both into FRAGMENT-MAJOR planes
-// (frag_off): a wave's operand load is one contiguous 1 KB block.  No LDS, no barrier: a wave owns 32 rows x 32 gate columns x
-// one K slice, four k-steps of operands in flight; partial sums per K slice as before (lstm_cell_kernel adds them in slice
-// order).  Measured (configs[3], same box): a gate GEMM 22.5 -> 17.8 us (the exact-f32 kernel's 51 426 launches average 17.6 us
-// over gate AND the smaller pred_proj GEMMs), beam-8 decode 122 -> 112 ms, greedy 70 -> 60 ms.  Not the ~6 us its MFMA time
-// would allow: 6 bytes per weight now come from beyond L2 per launch (50 MB at K = 2048) -- two W planes instead of three or a
-// deeper prefetch moved it by 4 % / 0 % (EXPERIMENTS.md).  MS_RNNT_GATES_F32=1 keeps the exact-f32 MFMA path.
-// Fragment-major operand layouts of the split gate GEMM: element (row, k) of a [rows, K] matrix sits where the lane that
-// needs it (row % 32, (k % 16) / 8) finds its 8 consecutive k next to the other 63 lanes' -- a wave's operand load is then
-// one contiguous block (1 KB of bf16, 2 KB of float32) instead of 32 row segments of 32 / 64 bytes (row-major operands made
-// the kernel address-coalescing-bound: 32 us per launch).
+// ---- split-operand GEMMs.  float32 MFMA issues at 1/16 of the bf16 rate, so every float32 operand is written as THREE bf16
+// values h + m + l (8 + 8 + 8 significand bits: an exact decomposition) and the product keeps the six terms down to 2^-24
+// relative (hh, hm, mh, mm, hl, lh), accumulated in float32: float32-grade products at 6/16 of the float32 MFMA time.  The
+// weights are split once per decode call (pack_cat3_kernel, pack_rows3_kernel), the rows by the kernels that produce them
+// (store_split3 / store_split), both into FRAGMENT-MAJOR planes: element (row, k) of a [rows, K] matrix sits where the lane
+// that needs it (row % 32, (k % 16) / 8) finds its 8 consecutive k next to the other 63 lanes' -- a wave's operand load is then
+// one contiguous 1 KB block instead of 32 row segments of 32 bytes (row-major operands made the GEMM address-coalescing-bound:
+// 32 us per launch against 17.8).  No LDS, no barrier in the K loop (split_contract): a wave owns 32 rows x 32 weight rows x
+// one K slice.  What binds is the operand pull -- 6 bytes per weight from beyond L2 per launch (EXPERIMENTS.md).
 __host__ __device__ __forceinline__ size_t frag_off(int row, int k, int K) {
   return ((((size_t)(row >> 5) * (K >> 4) + (k >> 4)) * 2 + ((k >> 3) & 1)) * 32 + (row & 31)) * 8 + (k & 7);
 }
@@ -202,16 +207,80 @@ __device__ __forceinline__ void store_split(unsigned short* planes, size_t plane
 
 __device__ __forceinline__ unsigned bf16_rne(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x); }
 
-// unit_major (the fused layer kernel): gate row g H + u is stored as row (u / 8) 32 + g 8 + u % 8, so that the 32 rows of a
-// 32-row fragment group are the four gates of eight hidden units
+// The K loop of every split-operand GEMM here: one wave's x[32 rows, 16 nks] . w[32 rows, 16 nks]^T.  xp / w0 point at this
+// lane's 8 elements of the first k-step in plane 0 (a k-step further is 512 elements further, a plane xplane / wplane); PF
+// k-steps of operands are in flight (the weights come from beyond L2).  TWO: two fp16 planes hi + lo and three products instead
+// of three bf16 planes and six (a template parameter: as a uniform run-time flag it cost the three-plane form 10 %).  GUARD:
+// a lane with !row_ok contracts zeros instead of loading x (x planes that are not padded to whole row groups).
+// Result: D[row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the wave's 32][col = lane & 31].
+template <bool TWO, bool GUARD>
+__device__ __forceinline__ f32x16r split_contract(const unsigned short* xp, size_t xplane, const unsigned short* w0, size_t wplane,
+                                                  int nks, bool row_ok) {
+  constexpr int NP = TWO ? 2 : 3;
+  constexpr int PF = TWO ? MS_RNNT_PF2 : 4;
+  f32x16r acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  u32x4r xf[PF][NP], wf[PF][NP];
+  auto load = [&](int slot, int ks) {                           // one k-step further: 2 halves x 32 rows x 8 elements
+#pragma unroll
+    for (int pl = 0; pl < NP; ++pl) {
+      if constexpr (GUARD) xf[slot][pl] = u32x4r{0u, 0u, 0u, 0u};
+      if (!GUARD || row_ok) xf[slot][pl] = *reinterpret_cast<const u32x4r*>(xp + (size_t)pl * xplane + (size_t)ks * 512);
+      wf[slot][pl] = *reinterpret_cast<const u32x4r*>(w0 + (size_t)pl * wplane + (size_t)ks * 512);
+    }
+  };
+  auto step = [&](int slot) {                                   // smallest terms first
+    if constexpr (TWO) {                                        // hi.hi + lo.hi + hi.lo in fp16
+      const f16x8r wh_ = __builtin_bit_cast(f16x8r, wf[slot][0]), wl_ = __builtin_bit_cast(f16x8r, wf[slot][1]);
+      const f16x8r xh_ = __builtin_bit_cast(f16x8r, xf[slot][0]), xl_ = __builtin_bit_cast(f16x8r, xf[slot][1]);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl_, wh_, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh_, wl_, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh_, wh_, acc, 0, 0, 0);
+    } else {
+      const bf16x8r bh = __builtin_bit_cast(bf16x8r, wf[slot][0]), bm = __builtin_bit_cast(bf16x8r, wf[slot][1]);
+      const bf16x8r bl = __builtin_bit_cast(bf16x8r, wf[slot][2]);
+      const bf16x8r xh = __builtin_bit_cast(bf16x8r, xf[slot][0]), xm = __builtin_bit_cast(bf16x8r, xf[slot][1]);
+      const bf16x8r xl = __builtin_bit_cast(bf16x8r, xf[slot][2]);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, bh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bl, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bm, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bm, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bh, acc, 0, 0, 0);
+    }
+  };
+#pragma unroll
+  for (int j = 0; j < PF; ++j)
+    if (j < nks) load(j, j);
+  for (int ks = 0; ks < nks; ks += PF) {
+#pragma unroll
+    for (int j = 0; j < PF; ++j)
+      if (ks + j < nks) {
+        step(j);
+        if (ks + j + PF < nks) load(j, ks + j + PF);
+      }
+  }
+  return acc;
+}
+
+__device__ __forceinline__ void lstm_cell(const float pre[4], float c_old, float& h_new, float& c_new) {
+  const float gi = 1.f / (1.f + expf(-pre[0])), gf = 1.f / (1.f + expf(-pre[1]));
+  const float gg = tanhf(pre[2]), go = 1.f / (1.f + expf(-pre[3]));
+  c_new = gf * c_old + gi * gg;
+  h_new = go * tanhf(c_new);
+}
+
+// [W_ih | W_hh] rows of one layer as three bf16 planes, unit-major (the fused layer kernel): gate row g H + u is stored as row
+// (u / 8) 32 + g 8 + u % 8, so that the 32 rows of a 32-row fragment group are the four gates of eight hidden units
 __global__ void pack_cat3_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, const float* __restrict__ b_ih,
                                  const float* __restrict__ b_hh, unsigned short* __restrict__ planes, float* __restrict__ bcat,
-                                 int H, int In, int unit_major) {
+                                 int H, int In) {
   const int src_row = blockIdx.x;  // 4H rows
   const int K = In + H;
   const size_t plane = (size_t)4 * H * K;
   const int gate_ = src_row / H, unit_ = src_row % H;
-  const int row = unit_major ? (unit_ >> 3) * 32 + gate_ * 8 + (unit_ & 7) : src_row;
+  const int row = (unit_ >> 3) * 32 + gate_ * 8 + (unit_ & 7);
   for (int k = threadIdx.x; k < K; k += blockDim.x) {
     const float x = k < In ? w_ih[(size_t)src_row * In + k] : w_hh[(size_t)src_row * H + (k - In)];
     const unsigned h = bf16_rne(x);
@@ -224,75 +293,6 @@ __global__ void pack_cat3_kernel(const float* __restrict__ w_ih, const float* __
     planes[2 * plane + o] = (unsigned short)l;
   }
   if (threadIdx.x == 0) bcat[row] = (b_ih ? b_ih[src_row] : 0.f) + (b_hh ? b_hh[src_row] : 0.f);
-}
-
-// grid (N4 / 64, nsplit, cdiv(R, 128)), 512 threads; parts [nsplit][R][N4]; K % (16 * nsplit) == 0, N4 % 64 == 0.
-// Eight waves: wave = (row group of 32, column tile of 32); with eight K slices that is four waves per SIMD, which is what
-// hides the L2 latency of a k-step's operands (a first form with four waves of 32 x 64 and one k-step of prefetch ran at the
-// latency: 31.8 us per launch against 17.6 for the exact-f32 kernel).
-__global__ __launch_bounds__(512) void pred_gates_split_kernel(const unsigned short* __restrict__ x, size_t xplane,
-                                                               const unsigned short* __restrict__ wp,
-                                                               const float* __restrict__ bias, float* __restrict__ parts, int R,
-                                                               int K, int N4, int nsplit) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int l31 = lane & 31, half = lane >> 5;
-  const int rg = wave & 3, nt = wave >> 2;
-  const int n0 = blockIdx.x * 64 + nt * 32, z = blockIdx.y;
-  const int m = blockIdx.z * 128 + rg * 32 + l31;             // this lane's x row
-  const int kslice = K / nsplit, k0 = z * kslice;
-  const size_t wplane = (size_t)N4 * K;
-  const unsigned short* xp = x + frag_off(m, k0 + half * 8, K);          // x and W: three bf16 planes each, fragment-major
-  const unsigned short* w0 = wp + frag_off(n0 + l31, k0 + half * 8, K);
-  const bool row_ok = m < R;
-
-  f32x16r acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-  constexpr int PF = 4;                                        // k-steps of operands in flight (the weights come from beyond L2)
-  u32x4r xf[PF][3], wf[PF][3];
-  auto load = [&](int slot, int ks) {                           // one k-step further: 2 halves x 32 rows x 8 elements
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      xf[slot][pl] = u32x4r{0u, 0u, 0u, 0u};
-      if (row_ok) xf[slot][pl] = *reinterpret_cast<const u32x4r*>(xp + (size_t)pl * xplane + (size_t)ks * 512);
-      wf[slot][pl] = *reinterpret_cast<const u32x4r*>(w0 + (size_t)pl * wplane + (size_t)ks * 512);
-    }
-  };
-  auto step = [&](int slot) {
-    const bf16x8r bh = __builtin_bit_cast(bf16x8r, wf[slot][0]), bm = __builtin_bit_cast(bf16x8r, wf[slot][1]);
-    const bf16x8r bl = __builtin_bit_cast(bf16x8r, wf[slot][2]);
-    const bf16x8r xh = __builtin_bit_cast(bf16x8r, xf[slot][0]), xm = __builtin_bit_cast(bf16x8r, xf[slot][1]);
-    const bf16x8r xl = __builtin_bit_cast(bf16x8r, xf[slot][2]);
-    // smallest terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bh, acc, 0, 0, 0);
-  };
-  const int nks = kslice / 16;
-#pragma unroll
-  for (int j = 0; j < PF; ++j)
-    if (j < nks) load(j, j);
-  for (int ks = 0; ks < nks; ks += PF) {
-#pragma unroll
-    for (int j = 0; j < PF; ++j)
-      if (ks + j < nks) {
-        step(j);
-        if (ks + j + PF < nks) load(j, ks + j + PF);
-      }
-  }
-  // D[row = (r & 3) + 8 (r >> 2) + 4 half of the wave's 32][col = l31]
-  float* out = parts + (size_t)z * R * N4;
-  const int n = n0 + l31;
-  const float bv = (z == 0 && bias != nullptr) ? bias[n] : 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int mr = blockIdx.z * 128 + rg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-    if (mr < R) out[(size_t)mr * N4 + n] = acc[r] + bv;
-  }
 }
 
 // x0[r] = [embedding[label_r] | h[src_r][layer 0]]; rows without a request are zero.
@@ -317,8 +317,7 @@ __global__ void pred_gather_kernel(const float* __restrict__ embedding, const in
 // [h' | h[src][l+1]] or, after the last layer, the row of `htop`.
 __global__ void lstm_cell_kernel(const float* __restrict__ gates, const int32_t* __restrict__ ext_src,
                                  const int32_t* __restrict__ ext_dst, float* __restrict__ st_h, float* __restrict__ st_c,
-                                 float* __restrict__ xnext, float* __restrict__ htop, int H, int L, int l, int R, int nsplit,
-                                 int frag, size_t xplane) {
+                                 float* __restrict__ xnext, float* __restrict__ htop, int H, int L, int l, int R) {
   const int r = blockIdx.x;
   const int src = ext_src[r], dst = ext_dst[r];
   const float* g = gates + (size_t)r * 4 * H;
@@ -330,17 +329,14 @@ __global__ void lstm_cell_kernel(const float* __restrict__ gates, const int32_t*
     for (int gate = 0; gate < 4; ++gate) {
       float pz[KSPLIT];
 #pragma unroll
-      for (int z = 0; z < KSPLIT; ++z) pz[z] = z < nsplit ? g[z * part + gate * H + u] : 0.f;   // independent loads ...
+      for (int z = 0; z < KSPLIT; ++z) pz[z] = g[z * part + gate * H + u];   // independent loads ...
       float v = pz[0];
 #pragma unroll
-      for (int z = 1; z < KSPLIT; ++z)
-        if (z < nsplit) v += pz[z];                                                            // ... added in slice order
+      for (int z = 1; z < KSPLIT; ++z) v += pz[z];                           // ... added in slice order
       pre[gate] = v;
     }
-    const float gi = 1.f / (1.f + expf(-pre[0])), gf = 1.f / (1.f + expf(-pre[1]));
-    const float gg = tanhf(pre[2]), go = 1.f / (1.f + expf(-pre[3]));
-    const float c_new = gf * c_old + gi * gg;
-    const float h_new = go * tanhf(c_new);
+    float h_new, c_new;
+    lstm_cell(pre, c_old, h_new, c_new);
     float h_next_src = 0.f;
     if (l + 1 < L && dst >= 0 && src >= 0) h_next_src = st_h[((size_t)src * L + l + 1) * H + u];
     if (dst >= 0) {
@@ -348,27 +344,22 @@ __global__ void lstm_cell_kernel(const float* __restrict__ gates, const int32_t*
       st_c[((size_t)dst * L + l) * H + u] = c_new;
     }
     if (l + 1 < L) {
-      if (frag) {
-        store_split3(reinterpret_cast<unsigned short*>(xnext), xplane, frag_off(r, u, 2 * H), dst >= 0 ? h_new : 0.f);
-        store_split3(reinterpret_cast<unsigned short*>(xnext), xplane, frag_off(r, H + u, 2 * H), h_next_src);
-      } else {
-        xnext[(size_t)r * 2 * H + u] = dst >= 0 ? h_new : 0.f;
-        xnext[(size_t)r * 2 * H + H + u] = h_next_src;
-      }
+      xnext[(size_t)r * 2 * H + u] = dst >= 0 ? h_new : 0.f;
+      xnext[(size_t)r * 2 * H + H + u] = h_next_src;
     } else {
       htop[(size_t)r * H + u] = dst >= 0 ? h_new : 0.f;
     }
   }
 }
 
-// ---- one predictor layer in ONE launch (round 4): gate GEMM + cell.  The split-K gate GEMM left 4 x R x 4H partial sums in
-// memory for a second kernel to add (8.4 MB written and read back per layer-step at configs[3], 17.8 + 9.5 us and a kernel
+// ---- one predictor layer in ONE launch: split-operand gate GEMM + cell.  A split-K gate GEMM leaves 4 x R x 4H partial sums
+// in memory for a second kernel to add (8.4 MB written and read back per layer-step at configs[3], 17.8 + 9.5 us and a kernel
 // boundary, four times per frame: half of the beam decode).  Here a workgroup owns EIGHT hidden units -- their four gates are
 // the 32 rows of one fragment group of the unit-major weight planes (pack_cat3_kernel) -- and 32 RG hypothesis rows; its eight
 // waves split the rows into RG groups and K into 8 / RG slices, meet in LDS, and the workgroup applies the cell to its
 // (row, unit) pairs itself: c_old gathered from the source slot, (h, c) written to the destination slot, the next layer's
 // operand row [h' | h_src] (or the htop row) written as the GEMM wrote nothing.  Partial sums are added in slice order, slice 0
-// carrying the bias, as lstm_cell_kernel did with the K-slice launches.  256 workgroups at R = 128 (one per CU, each streaming
+// carrying the bias, as lstm_cell_kernel does with the K-slice launches.  256 workgroups at R = 128 (one per CU, each streaming
 // its 32 weight rows once), 128 at R <= 32.  The next layer's rows go to the OTHER x buffer: other workgroups still read this one.
 template <int RG>
 __global__ __launch_bounds__(512) void pred_layer_fused_kernel(const unsigned short* __restrict__ x, size_t xplane,
@@ -388,45 +379,7 @@ __global__ __launch_bounds__(512) void pred_layer_fused_kernel(const unsigned sh
   const size_t wplane = (size_t)4 * H * K;
   const unsigned short* xp = x + frag_off(m, k0 + half * 8, K);
   const unsigned short* w0 = wp + frag_off(b * 32 + l31, k0 + half * 8, K);
-  const bool row_ok = m < R;
-
-  f32x16r acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  constexpr int PF = 4;
-  u32x4r xf[PF][3], wf[PF][3];
-  auto load = [&](int slot, int ks) {
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      xf[slot][pl] = u32x4r{0u, 0u, 0u, 0u};
-      if (row_ok) xf[slot][pl] = *reinterpret_cast<const u32x4r*>(xp + (size_t)pl * xplane + (size_t)ks * 512);
-      wf[slot][pl] = *reinterpret_cast<const u32x4r*>(w0 + (size_t)pl * wplane + (size_t)ks * 512);
-    }
-  };
-  auto step = [&](int slot) {
-    const bf16x8r bh = __builtin_bit_cast(bf16x8r, wf[slot][0]), bm = __builtin_bit_cast(bf16x8r, wf[slot][1]);
-    const bf16x8r bl = __builtin_bit_cast(bf16x8r, wf[slot][2]);
-    const bf16x8r xh = __builtin_bit_cast(bf16x8r, xf[slot][0]), xm = __builtin_bit_cast(bf16x8r, xf[slot][1]);
-    const bf16x8r xl = __builtin_bit_cast(bf16x8r, xf[slot][2]);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, bh, acc, 0, 0, 0);   // smallest terms first (pred_gates_split_kernel)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bh, acc, 0, 0, 0);
-  };
-  const int nks = kslice / 16;
-#pragma unroll
-  for (int j = 0; j < PF; ++j)
-    if (j < nks) load(j, j);
-  for (int ks = 0; ks < nks; ks += PF) {
-#pragma unroll
-    for (int j = 0; j < PF; ++j)
-      if (ks + j < nks) {
-        step(j);
-        if (ks + j + PF < nks) load(j, ks + j + PF);
-      }
-  }
+  const f32x16r acc = split_contract<false, true>(xp, xplane, w0, wplane, kslice / 16, m < R);
   // D[row = (r & 3) + 8 (r >> 2) + 4 half of the wave's 32][col = l31 = gate * 8 + unit % 8]
 #pragma unroll
   for (int r = 0; r < 16; ++r) red[wave][(r & 3) + 8 * (r >> 2) + 4 * half][l31] = acc[r];
@@ -446,10 +399,8 @@ __global__ __launch_bounds__(512) void pred_layer_fused_kernel(const unsigned sh
   }
   const int src = ext_src[r], dst = ext_dst[r];
   const float c_old = (dst >= 0 && src >= 0) ? st_c[((size_t)src * L + l) * H + u] : 0.f;
-  const float gi = 1.f / (1.f + expf(-pre[0])), gf = 1.f / (1.f + expf(-pre[1]));
-  const float gg = tanhf(pre[2]), go = 1.f / (1.f + expf(-pre[3]));
-  const float c_new = gf * c_old + gi * gg;
-  const float h_new = go * tanhf(c_new);
+  float h_new, c_new;
+  lstm_cell(pre, c_old, h_new, c_new);
   float h_next_src = 0.f;
   if (l + 1 < L && dst >= 0 && src >= 0) h_next_src = st_h[((size_t)src * L + l + 1) * H + u];
   if (dst >= 0) {
@@ -604,57 +555,43 @@ __global__ __launch_bounds__(256) void joint_slots_kernel(const float* __restric
   }
 }
 
+// Everything the beam kernels of both sequences share, filled once per decode call.
 struct BeamP {
   const int32_t* lens;
-  const float* logp;
-  int32_t *A_cnt, *A_node, *A_slot;
+  int32_t *A_cnt, *A_node, *A_slot;     // this frame's live set (the rounds replace it in place: one workgroup per utterance)
   float* A_score;
+  int32_t *nA_cnt, *nA_node, *nA_slot;  // re-cut sequence: the next frame's, written by the frame end (its w workgroups per
+  float* nA_score;                      // utterance all READ this frame's set, so they must not write it)
   int32_t *B_cnt, *B_node, *B_slot;
   float* B_score;
   int32_t *ext_label, *ext_src, *ext_dst;
   int32_t *node_cnt, *node_parent, *node_label, *child;
-  int N, w, V, bcap, maxn, R;
+  float *st_h, *st_c, *pp;
+  const float* logp;            // round-4 sequence: joint_slots_kernel's log-probabilities
+  // re-cut sequence
+  float* G;
+  const float *E, *bias, *plog, *b_out;
+  unsigned short* hpl;          // [L][3][rpad * H] planes of the rows' new h of every layer
+  size_t hplane;                // rpad * H
+  int N, w, V, bcap, maxn, R, H, L, J, NS;
+  int two;                      // operand planes of the step's GEMMs: 0 = three bf16 (exact), 1 = two fp16 (store_split)
 };
 
-// One emission round of one utterance (one workgroup).  Everything the round needs is fetched by independent loads at
-// the top (one memory round trip: the words were written by the previous kernel, usually on another XCD), the list
-// surgery then runs in LDS, and the trie insertions of the picked extensions go out in parallel.
-__global__ __launch_bounds__(256) void beam_round_kernel(BeamP p, int t, int region, int first, int last) {
-  extern __shared__ __attribute__((aligned(16))) float cand[];  // [w * V1] log-probabilities, then candidate scores
-  __shared__ int wi[4];
-  __shared__ int pick_idx[32];
-  __shared__ float pick_val[32];
-  __shared__ int old_node[32], old_slot[32];
-  __shared__ float old_score[32];
-  __shared__ int b_node[128], b_slot[128];
-  __shared__ float b_score[128];
-  __shared__ int n_pick, next_node;
-  __shared__ int match_at[32];
-  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int w = p.w, V1 = p.V + 1, blank = p.V;
-  const int len_i = p.lens[i], cnt = p.A_cnt[i], bc0 = first ? 0 : p.B_cnt[i], nodes0 = p.node_cnt[i];
-  if (tid < w) {
-    old_node[tid] = p.A_node[i * w + tid];
-    old_slot[tid] = p.A_slot[i * w + tid];
-    old_score[tid] = p.A_score[i * w + tid];
-    p.ext_dst[i * w + tid] = -1;  // requests default to "none" (also for utterances that have ended)
-  }
-  if (tid < p.bcap) {
-    b_node[tid] = p.B_node[(size_t)i * p.bcap + tid];
-    b_score[tid] = p.B_score[(size_t)i * p.bcap + tid];
-    b_slot[tid] = p.B_slot[(size_t)i * p.bcap + tid];
-  }
-  for (int c = tid; c < w * V1; c += 256) cand[c] = p.logp[(size_t)i * w * V1 + c];
-  if (t >= len_i) return;
-  if (tid == 0) { n_pick = 0; next_node = nodes0; }
+// ---- the hypothesis-list rules, shared by both beam sequences.  All 256 threads of a workgroup call them; the arrays are LDS.
+
+// Blank transitions of one round into the LDS copy of B, in hypothesis order: same prefix (trie node) -> logaddexp, else append
+// (first arrival keeps its predictor state).  b_* hold B (bc0 entries), old_* the cnt live hypotheses, cand their
+// log-probabilities; the new count is returned through wi[0].  The live hypotheses' nodes are distinct (picks are distinct
+// (parent, label) pairs, the frame's first set comes out of B, whose nodes are distinct), so the hypotheses do not interact:
+// every (hypothesis, B entry) pair is compared at once and wave 0 merges / appends, an append's position = its rank among the
+// unmatched (thread 0 walking cnt x bc dependent LDS reads was ~10 of the round kernel's 14.7 us).  Should two live hypotheses
+// ever share a node the serial walk does what it always did.
+__device__ __forceinline__ void beam_blank_merge(int cnt, int bc0, int bcap, int V1, int blank, const float* cand, const int* old_node,
+                                                 const int* old_slot, const float* old_score, int* b_node, int* b_slot,
+                                                 float* b_score, int* match_at, int* wi, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
   if (tid < 32) match_at[tid] = -1;
   __syncthreads();
-  // blank transitions, in hypothesis order: same prefix (trie node) -> logaddexp, else append (first arrival keeps its
-  // predictor state).  The live hypotheses' nodes are distinct (picks are distinct (parent, label) pairs, the frame's first
-  // set comes out of B, whose nodes are distinct), so the hypotheses do not interact: every (hypothesis, B entry) pair is
-  // compared at once and wave 0 merges / appends, an append's position = its rank among the unmatched (round 4: thread 0
-  // walked cnt x bc dependent LDS reads, ~10 of the kernel's 14.7 us).  Should two live hypotheses ever share a node the
-  // serial walk below does what it always did.
   for (int idx = tid; idx < cnt * bc0; idx += 256) {
     const int j = idx / bc0, b = idx - j * bc0;
     if (b_node[b] == old_node[j]) match_at[j] = b;
@@ -675,14 +612,13 @@ __global__ __launch_bounds__(256) void beam_round_kernel(BeamP p, int t, int reg
             if (b_node[b] == old_node[jj]) { at = b; break; }
           if (at >= 0) {
             b_score[at] = logaddexp32(b_score[at], s);
-          } else if (bc < p.bcap) {
+          } else if (bc < bcap) {
             b_node[bc] = old_node[jj];
             b_score[bc] = s;
             b_slot[bc] = old_slot[jj];
             ++bc;
           }
         }
-        p.B_cnt[i] = bc;
         wi[0] = bc;
       }
     } else {
@@ -695,33 +631,27 @@ __global__ __launch_bounds__(256) void beam_round_kernel(BeamP p, int t, int reg
         const float s = old_score[j] + cand[j * V1 + blank];
         if (at >= 0) {
           b_score[at] = logaddexp32(b_score[at], s);
-        } else if (pos < p.bcap) {
+        } else if (pos < bcap) {
           b_node[pos] = old_node[j];
           b_score[pos] = s;
           b_slot[pos] = old_slot[j];
         }
       }
-      if (lane == 0) {
-        const int bc = min(bc0 + (int)__popcll(um), p.bcap);
-        p.B_cnt[i] = bc;
-        wi[0] = bc;
-      }
-    }
-    if (lane == 0 && last) p.A_cnt[i] = 0;
-  }
-  __syncthreads();
-  {
-    const int bc = wi[0];
-    if (tid < bc) {
-      p.B_node[(size_t)i * p.bcap + tid] = b_node[tid];
-      p.B_score[(size_t)i * p.bcap + tid] = b_score[tid];
-      p.B_slot[(size_t)i * p.bcap + tid] = b_slot[tid];
+      if (lane == 0) wi[0] = min(bc0 + (int)__popcll(um), bcap);
     }
   }
-  if (last) return;
   __syncthreads();
-  // label extensions: the w best of cnt * V1 candidates (score desc, ties -> lowest flat index), blank and
-  // non-finite scores excluded
+}
+
+// Label extensions of utterance i: the w best of cnt * V1 candidates (score desc, ties -> lowest flat index), blank and
+// non-finite scores excluded, are inserted into the trie and become the live set and the predictor requests (state slots in
+// `region`).  cand holds the log-probabilities and is overwritten; *next_node must hold node_cnt[i].  Returns the number of
+// picks; *next_node is then the trie's new size (the caller stores both).
+__device__ __forceinline__ int beam_extend(const BeamP& p, int i, int cnt, int region, float* cand, const int* old_node,
+                                           const int* old_slot, const float* old_score, int* pick_idx, float* pick_val, int* n_pick,
+                                           int* next_node, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int w = p.w, V1 = p.V + 1, blank = p.V;
   const int C = cnt * V1;
   for (int c = tid; c < C; c += 256) {
     const int j = c / V1, k = c - j * V1;
@@ -729,8 +659,8 @@ __global__ __launch_bounds__(256) void beam_round_kernel(BeamP p, int t, int reg
     cand[c] = (k == blank || !isfinite(s)) ? -INFINITY : s;
   }
   __syncthreads();
-  // the w best, one after the other, by ONE wave (round 4: all four waves with two barriers and a serial merge per pick took
-  // most of the kernel's 14.7 us): a lane scans its candidates, the wave reduces (value desc, ties -> lowest flat index), lane 0
+  // the w best, one after the other, by ONE wave (all four waves with two barriers and a serial merge per pick took most of
+  // the round kernel's 14.7 us): a lane scans its candidates, the wave reduces (value desc, ties -> lowest flat index), lane 0
   // records the pick and removes it -- a wave's LDS operations execute in order, so the next scan sees the removal
   if (wave == 0) {
     int npk = 0;
@@ -755,10 +685,10 @@ __global__ __launch_bounds__(256) void beam_round_kernel(BeamP p, int t, int reg
       }
       ++npk;
     }
-    if (lane == 0) n_pick = npk;
+    if (lane == 0) *n_pick = npk;
   }
   __syncthreads();
-  const int np = n_pick;
+  const int np = *n_pick;
   if (tid < np) {
     // distinct picks are distinct (parent, label) pairs, so their trie insertions are independent; node numbers are
     // identities only, an atomic counter hands them out
@@ -768,7 +698,7 @@ __global__ __launch_bounds__(256) void beam_round_kernel(BeamP p, int t, int reg
     int32_t* ch = p.child + ((size_t)i * p.maxn + parent) * p.V + k;
     int node = *ch;
     if (node < 0) {
-      node = atomicAdd(&next_node, 1);
+      node = atomicAdd(next_node, 1);
       if (node < p.maxn) {
         p.node_parent[(size_t)i * p.maxn + node] = parent;
         p.node_label[(size_t)i * p.maxn + node] = k;
@@ -786,34 +716,15 @@ __global__ __launch_bounds__(256) void beam_round_kernel(BeamP p, int t, int reg
     p.ext_dst[i * w + q] = slot;
   }
   __syncthreads();
-  if (tid == 0) {
-    p.A_cnt[i] = np;
-    p.node_cnt[i] = min(next_node, p.maxn);
-  }
+  return np;
 }
 
-// End of frame t: the beam_width best entries of B (stable, descending) become the live set of the next frame; their
-// predictor states are copied into frame-start region (t + 1) & 1.  Grid (w, N): every workgroup repeats the (cheap, LDS)
-// selection and moves ONE survivor's state with all its loads in flight at once.
-__global__ __launch_bounds__(256) void beam_frame_end_kernel(BeamP p, float* st_h, float* st_c, float* pp, int t, int LH, int J) {
-  __shared__ int b_node[128], b_slot[128];
-  __shared__ float b_score[128];
-  __shared__ int sel_src[32], sel_node[32];
-  __shared__ float sel_score[32];
-  __shared__ int n_sel;
-  const int q = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
-  const int w = p.w;
-  const int len_i = p.lens[i], bc = p.B_cnt[i];
-  if (tid < p.bcap) {
-    b_node[tid] = p.B_node[(size_t)i * p.bcap + tid];
-    b_score[tid] = p.B_score[(size_t)i * p.bcap + tid];
-    b_slot[tid] = p.B_slot[(size_t)i * p.bcap + tid];
-  }
-  if (t >= len_i) return;
-  __syncthreads();
-  // the beam_width best of B, one after the other (first maximum = earliest arrival among equals), by ONE wave: a lane holds
-  // entries lane and lane + 64, the wave reduces (an entry before none, score desc, index asc), the owner marks its entry taken
-  // (round 4: thread 0 walked w x bc dependent LDS reads, ~9 us, in every one of the w x N workgroups)
+// The w best of B's bc entries, one after the other (first maximum = earliest arrival among equals), by ONE wave: a lane holds
+// entries lane and lane + 64, the wave reduces (an entry before none, score desc, index asc), the owner marks its entry taken
+// (thread 0 walking w x bc dependent LDS reads was ~9 us in every one of the frame end's w x N workgroups).  Returns the number
+// selected; sel_* hold their slots, nodes and scores in order.
+__device__ __forceinline__ int beam_select(int bc, int w, const int* b_node, const int* b_slot, const float* b_score, int* sel_src,
+                                           int* sel_node, float* sel_score, int* n_sel, int tid) {
   if (tid < 64) {
     const int lane = tid;
     const float s0 = lane < bc ? b_score[lane] : 0.f, s1 = lane + 64 < bc ? b_score[lane + 64] : 0.f;
@@ -844,10 +755,86 @@ __global__ __launch_bounds__(256) void beam_frame_end_kernel(BeamP p, float* st_
       }
       ++ns;
     }
-    if (lane == 0) n_sel = ns;
+    if (lane == 0) *n_sel = ns;
   }
   __syncthreads();
-  const int ns = n_sel;
+  return *n_sel;
+}
+
+// One emission round of one utterance (one workgroup).  Everything the round needs is fetched by independent loads at
+// the top (one memory round trip: the words were written by the previous kernel, usually on another XCD), the list
+// surgery then runs in LDS, and the trie insertions of the picked extensions go out in parallel.
+__global__ __launch_bounds__(256) void beam_round_kernel(BeamP p, int t, int region, int first, int last) {
+  extern __shared__ __attribute__((aligned(16))) float cand[];  // [w * V1] log-probabilities, then candidate scores
+  __shared__ int wi[4];
+  __shared__ int pick_idx[32];
+  __shared__ float pick_val[32];
+  __shared__ int old_node[32], old_slot[32];
+  __shared__ float old_score[32];
+  __shared__ int b_node[128], b_slot[128];
+  __shared__ float b_score[128];
+  __shared__ int n_pick, next_node;
+  __shared__ int match_at[32];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int w = p.w, V1 = p.V + 1, blank = p.V;
+  const int len_i = p.lens[i], cnt = p.A_cnt[i], bc0 = first ? 0 : p.B_cnt[i], nodes0 = p.node_cnt[i];
+  if (tid < w) {
+    old_node[tid] = p.A_node[i * w + tid];
+    old_slot[tid] = p.A_slot[i * w + tid];
+    old_score[tid] = p.A_score[i * w + tid];
+    p.ext_dst[i * w + tid] = -1;  // requests default to "none" (also for utterances that have ended)
+  }
+  if (tid < p.bcap) {
+    b_node[tid] = p.B_node[(size_t)i * p.bcap + tid];
+    b_score[tid] = p.B_score[(size_t)i * p.bcap + tid];
+    b_slot[tid] = p.B_slot[(size_t)i * p.bcap + tid];
+  }
+  for (int c = tid; c < w * V1; c += 256) cand[c] = p.logp[(size_t)i * w * V1 + c];
+  if (t >= len_i) return;
+  if (tid == 0) { n_pick = 0; next_node = nodes0; }
+  beam_blank_merge(cnt, bc0, p.bcap, V1, blank, cand, old_node, old_slot, old_score, b_node, b_slot, b_score, match_at, wi, tid);
+  {
+    const int bc = wi[0];
+    if (tid == 0) {
+      p.B_cnt[i] = bc;
+      if (last) p.A_cnt[i] = 0;
+    }
+    if (tid < bc) {
+      p.B_node[(size_t)i * p.bcap + tid] = b_node[tid];
+      p.B_score[(size_t)i * p.bcap + tid] = b_score[tid];
+      p.B_slot[(size_t)i * p.bcap + tid] = b_slot[tid];
+    }
+  }
+  if (last) return;
+  __syncthreads();
+  const int np = beam_extend(p, i, cnt, region, cand, old_node, old_slot, old_score, pick_idx, pick_val, &n_pick, &next_node, tid);
+  if (tid == 0) {
+    p.A_cnt[i] = np;
+    p.node_cnt[i] = min(next_node, p.maxn);
+  }
+}
+
+// End of frame t: the beam_width best entries of B (stable, descending) become the live set of the next frame; their
+// predictor states are copied into frame-start region (t + 1) & 1.  Grid (w, N): every workgroup repeats the (cheap, LDS)
+// selection and moves ONE survivor's state with all its loads in flight at once.
+__global__ __launch_bounds__(256) void beam_frame_end_kernel(BeamP p, int t) {
+  __shared__ int b_node[128], b_slot[128];
+  __shared__ float b_score[128];
+  __shared__ int sel_src[32], sel_node[32];
+  __shared__ float sel_score[32];
+  __shared__ int n_sel;
+  const int q = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
+  const int w = p.w, LH = p.L * p.H, J = p.J;
+  float *st_h = p.st_h, *st_c = p.st_c, *pp = p.pp;
+  const int len_i = p.lens[i], bc = p.B_cnt[i];
+  if (tid < p.bcap) {
+    b_node[tid] = p.B_node[(size_t)i * p.bcap + tid];
+    b_score[tid] = p.B_score[(size_t)i * p.bcap + tid];
+    b_slot[tid] = p.B_slot[(size_t)i * p.bcap + tid];
+  }
+  if (t >= len_i) return;
+  __syncthreads();
+  const int ns = beam_select(bc, w, b_node, b_slot, b_score, sel_src, sel_node, sel_score, &n_sel, tid);
   if (q == 0 && tid == 0) p.A_cnt[i] = ns;
   if (q >= ns) return;
   const size_t src = (size_t)sel_src[q], dst = (size_t)((t + 1) & 1) * p.R + i * w + q;
@@ -1006,25 +993,29 @@ GreedyPoll* greedy_poll() {
 
 
 // =====================================================================================================================
-// The beam decode's predictor, round 5 (154 us per frame in 16 dependent launches).  The same
-// arithmetic -- every float32 product as an exact three-way bf16 split, float32 accumulation -- cut differently:
+// The re-cut beam sequence (the round-4 sequence spent 154 us per frame in 16 dependent launches).  The same arithmetic --
+// every float32 product as a split-operand product, float32 accumulation -- cut differently:
 //
 //   gates_0 = W_ih0 . emb[label] + W_hh0 . h0[parent] + b0      gates_l = W_ihl . h'_{l-1} + W_hhl . h_l[parent] + b_l
 //             `---- E[label] ---'  `--- G_0[parent] ---'                                    `--- G_l[parent] ---'
 //
 //   * E = W_ih0 . emb + b0 is a table of V + 1 rows, made once per decode;
 //   * G_l[slot] = W_hhl . h_l[slot] depends on a STATE only, not on what is appended to it: it is computed once per state,
-//     right after the state is made (pred_gemm3_kernel<.., false>, all layers in one launch), and kept beside it in the pool;
-//   * so a predictor step's chain is: round -> cell 0 of the picks (elementwise: E[label] + G_0[parent], in the round kernel
-//     itself) -> W_ihl . h'_{l-1} + G_l[parent] -> cell l (pred_gemm3_kernel<.., true>, K = H instead of In + H) -> joint;
-//   * pred_proj and the joint network are ONE kernel (beam2_joint_kernel): a workgroup owns 64 hypothesis rows x 32 joint
+//     right after the state is made (pred_gemm3_body<false, ..>), and kept beside it in the pool;
+//   * so a predictor step's chain is: round -> cell 0 of the picks (elementwise: E[label] + G_0[parent], beam2_cell0_kernel)
+//     -> W_ihl . h'_{l-1} + G_l[parent] -> cell l (pred_gemm3_body<true, ..>, K = H instead of In + H) -> joint;
+//   * G is not on that chain, so it rides in launches that are: G of layer l - 1 beside cell l (pred_gemm3_cell_g_kernel), G of
+//     the top layer beside the step's joint (beam2_joint_g_kernel);
+//   * pred_proj and the joint network are ONE kernel (beam2_joint_kernel): a workgroup owns 32 or 64 hypothesis rows x 32 joint
 //     units, contracts h_top against its W_pred rows, adds the encoder projection, applies tanh and leaves the 32-unit partial
 //     sums of the output layer; the round kernel adds the J / 32 partials in slice order and normalises;
 //   * the last round of a frame and the frame end are one kernel (beam2_frame_end_kernel).
-// A frame at max_symbols = 3, two layers: 10 launches (joint, round | layer 1, G, joint, round | layer 1, G, joint, frame end).
-// Shapes: H % 64 == 0, J % 32 == 0; anything else takes the round-4 sequence.  MS_RNNT_V2=0 (read per call) selects it too.
+// A frame at max_symbols = 3, two layers: 10 launches (joint, round | cell 0, cell 1 + G_0, joint + G_1, round | cell 0,
+// cell 1 + G_0, joint + G_1, frame end).  Shapes: H % 64 == 0, J % 32 == 0 and the LDS conditions at the gate in
+// ms_rnnt_decode; anything else takes the round-4 sequence.
 
-// rows [rows][K] float32 -> three fragment-major bf16 planes; unit_major: gate row g H + u -> row (u / 8) 32 + g 8 + u % 8
+// rows [rows][K] float32 -> fragment-major operand planes (store_split); H_units > 0 = unit-major: gate row g H + u -> row
+// (u / 8) 32 + g 8 + u % 8
 __global__ void pack_rows3_kernel(const float* __restrict__ w, unsigned short* __restrict__ planes, int rows, int K, int H_units, int two) {
   const int src_row = blockIdx.x;
   int row = src_row;
@@ -1049,35 +1040,10 @@ __global__ void unit_major_add_kernel(const float* __restrict__ tab, const float
   for (int v = 0; v < nv; ++v) out[(size_t)v * 4 * H + row] = tab[(size_t)v * 4 * H + src] + bias;
 }
 
-struct Beam2P {
-  const int32_t* lens;
-  int32_t *A_cnt, *A_node, *A_slot;     // this frame's live set (the rounds replace it in place: one workgroup per utterance)
-  float* A_score;
-  int32_t *nA_cnt, *nA_node, *nA_slot;  // the next frame's, written by the frame end (its w workgroups per utterance all READ
-  float* nA_score;                      // this frame's set, so they must not write it)
-  int32_t *B_cnt, *B_node, *B_slot;
-  float* B_score;
-  int32_t *ext_label, *ext_src, *ext_dst;
-  int32_t *node_cnt, *node_parent, *node_label, *child;
-  float *st_h, *st_c, *pp, *G;
-  const float *E, *bias, *plog, *b_out;
-  unsigned short* hpl;          // [L][3][rpad * H] planes of the rows' new h of every layer
-  size_t hplane;                // rpad * H
-  int N, w, V, bcap, maxn, R, H, L, J, NS;
-  int two;                      // operand planes of the step's GEMMs: 0 = three bf16 (exact), 1 = two fp16 (store_split)
-};
-
-__device__ __forceinline__ void lstm_cell(const float pre[4], float c_old, float& h_new, float& c_new) {
-  const float gi = 1.f / (1.f + expf(-pre[0])), gf = 1.f / (1.f + expf(-pre[1]));
-  const float gg = tanhf(pre[2]), go = 1.f / (1.f + expf(-pre[3]));
-  c_new = gf * c_old + gi * gg;
-  h_new = go * tanhf(c_new);
-}
-
 // cell 0 of every request row (label k appended to the state in slot src; -1 = the zero state): E[k] + G_0[src].  One
 // workgroup per row; a thread's units' loads are all issued before the first is used (a unit at a time waited for an L2 round
 // trip per unit: 40 us inside the round kernel).
-__global__ __launch_bounds__(256) void beam2_cell0_kernel(Beam2P p) {
+__global__ __launch_bounds__(256) void beam2_cell0_kernel(BeamP p) {
   const int r = blockIdx.x, tid = threadIdx.x;
   const int dst = p.ext_dst[r], src = p.ext_src[r], lab = p.ext_label[r];
   if (dst < 0) return;
@@ -1117,12 +1083,12 @@ __global__ __launch_bounds__(256) void beam2_cell0_kernel(Beam2P p) {
 }
 
 // acc[64 rows x 32 weight rows] over K = H for one (weight-row group b, row block rb): eight waves = 2 row groups x 4 K
-// slices, three-way split products (pred_layer_fused_kernel's loop), partial sums met in LDS in slice order.
+// slices, split-operand products (split_contract), partial sums met in LDS in slice order.
 // CELL: weight rows = W_ih of layer l (unit-major), x = the rows' new h of layer l - 1; pre = sum + bias + G_l[src] -> cell
 //       -> state of the destination slot, the rows' new h of layer l as planes.
-// !CELL: blockIdx.z = layer; weight rows = W_hh of that layer, x = the rows' new h of that layer; G_l[dst] = sum.
+// !CELL: weight rows = W_hh of layer l, x = the rows' new h of that layer; G_l[dst] = sum.
 template <bool CELL, int RG, bool TWO>
-__device__ __forceinline__ void pred_gemm3_body(const Beam2P& p, const unsigned short* __restrict__ wp_base, int l, int b, int rb,
+__device__ __forceinline__ void pred_gemm3_body(const BeamP& p, const unsigned short* __restrict__ wp_base, int l, int b, int rb,
                                                 float (*red)[32][33]) {
   constexpr int KQ = 8 / RG;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1146,53 +1112,7 @@ __device__ __forceinline__ void pred_gemm3_body(const Beam2P& p, const unsigned 
   const bool epi = t < 256 * RG && r < R;
   const int src = p.ext_src[min(r, R - 1)], dst = p.ext_dst[min(r, R - 1)];
 
-  f32x16r acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  constexpr int PF = TWO ? MS_RNNT_PF2 : 4;                         // k-steps of operands in flight (two-plane form: registers for eight)
-  u32x4r xf[PF][TWO ? 2 : 3], wf[PF][TWO ? 2 : 3];
-  constexpr int two = TWO ? 1 : 0;                                   // two fp16 planes instead of three bf16 (a template parameter: as a
-                                                                     // uniform run-time flag it cost the three-plane form 10 %)
-  auto load = [&](int slot, int ks) {
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      if (pl >= (TWO ? 2 : 3)) continue;
-      xf[slot][pl] = *reinterpret_cast<const u32x4r*>(xp + (size_t)pl * p.hplane + (size_t)ks * 512);
-      wf[slot][pl] = *reinterpret_cast<const u32x4r*>(w0 + (size_t)pl * wplane + (size_t)ks * 512);
-    }
-  };
-  auto step = [&](int slot) {
-    if constexpr (TWO) {     // hi.hi + lo.hi + hi.lo in fp16 (smallest terms first)
-      const f16x8r wh_ = __builtin_bit_cast(f16x8r, wf[slot][0]), wl_ = __builtin_bit_cast(f16x8r, wf[slot][1]);
-      const f16x8r xh_ = __builtin_bit_cast(f16x8r, xf[slot][0]), xl_ = __builtin_bit_cast(f16x8r, xf[slot][1]);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl_, wh_, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh_, wl_, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh_, wh_, acc, 0, 0, 0);
-    } else {
-    const bf16x8r bh = __builtin_bit_cast(bf16x8r, wf[slot][0]), bm = __builtin_bit_cast(bf16x8r, wf[slot][1]);
-    const bf16x8r bl = __builtin_bit_cast(bf16x8r, wf[slot][2]);
-    const bf16x8r xh = __builtin_bit_cast(bf16x8r, xf[slot][0]), xm = __builtin_bit_cast(bf16x8r, xf[slot][1]);
-    const bf16x8r xl = __builtin_bit_cast(bf16x8r, xf[slot][2]);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, bh, acc, 0, 0, 0);   // smallest terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bh, acc, 0, 0, 0);
-    }
-  };
-  const int nks = kslice / 16;
-#pragma unroll
-  for (int j = 0; j < PF; ++j)
-    if (j < nks) load(j, j);
-  for (int ks = 0; ks < nks; ks += PF) {
-#pragma unroll
-    for (int j = 0; j < PF; ++j)
-      if (ks + j < nks) {
-        step(j);
-        if (ks + j + PF < nks) load(j, ks + j + PF);
-      }
-  }
+  const f32x16r acc = split_contract<TWO, false>(xp, p.hplane, w0, wplane, kslice / 16, true);
   // the cell's other inputs (bias, G of the source state, its c) are on their way while the partial sums meet in LDS
   const bool serve = epi && dst >= 0;                                 // a request in this row
   float bias_v[4] = {0.f, 0.f, 0.f, 0.f}, g_v[4] = {0.f, 0.f, 0.f, 0.f}, c_old = 0.f;
@@ -1239,24 +1159,18 @@ __device__ __forceinline__ void pred_gemm3_body(const Beam2P& p, const unsigned 
 // new h of layer l - 1 -- so they are one launch, blockIdx.z = 0 / 1: 2 x H / 8 workgroups fill the chip where the cell GEMM
 // alone used half of it, and the joint's launch carries only the top layer's G (27.7 -> ~19 us).  Same bodies, same sums.
 template <int RG, bool TWO>
-__global__ __launch_bounds__(512) void pred_gemm3_cell_g_kernel(Beam2P p, const unsigned short* __restrict__ wih, const unsigned short* __restrict__ whh,
+__global__ __launch_bounds__(512) void pred_gemm3_cell_g_kernel(BeamP p, const unsigned short* __restrict__ wih, const unsigned short* __restrict__ whh,
                                                                  int l_cell) {
   __shared__ float red[8][32][33];
   if (blockIdx.z == 0) pred_gemm3_body<true, RG, TWO>(p, wih, l_cell, blockIdx.x, blockIdx.y, red);
   else pred_gemm3_body<false, RG, TWO>(p, whh, l_cell - 1, blockIdx.x, blockIdx.y, red);
 }
 
-template <bool CELL, int RG, bool TWO>
-__global__ __launch_bounds__(512) void pred_gemm3_kernel(Beam2P p, const unsigned short* __restrict__ wp_base, int l_cell) {
-  __shared__ float red[8][32][33];
-  pred_gemm3_body<CELL, RG, TWO>(p, wp_base, CELL ? l_cell : (int)blockIdx.z, blockIdx.x, blockIdx.y, red);
-}
-
 // pred_proj + joint: grid (J / 32, cdiv(R, 32 RG)), 512 threads (RG row groups of 32 x 8 / RG K slices).  pp[slot][j] = W_pred[j] . h_top of a row whose state is new
 // (`gemm` != 0 and ext_dst[r] >= 0: committed to the pool), else the pool's; z = tanh(enc_p[t, i, j] + pp); the output
 // layer's partial sums over this workgroup's 32 joint units go to plog[slice][r][v].
 template <int RG, bool TWO>
-__device__ __forceinline__ void beam2_joint_body(const Beam2P& p, const unsigned short* __restrict__ wpred, const float* __restrict__ enc_p,
+__device__ __forceinline__ void beam2_joint_body(const BeamP& p, const unsigned short* __restrict__ wpred, const float* __restrict__ enc_p,
                                                  const float* __restrict__ w_out, float* __restrict__ plog, int t, int gemm, int js, int rb,
                                                  float (*red)[32][33], float (*zs)[33], float* wo) {
   constexpr int KQ = 8 / RG, ROWS = 32 * RG;
@@ -1293,51 +1207,7 @@ __device__ __forceinline__ void beam2_joint_body(const Beam2P& p, const unsigned
     const int kslice = K / KQ, k0 = kq * kslice;
     const unsigned short* xp = x + frag_off(m, k0 + half * 8, K);
     const unsigned short* w0 = wpred + frag_off(js * 32 + l31, k0 + half * 8, K);
-    f32x16r acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    constexpr int PF = TWO ? MS_RNNT_PF2 : 4;
-    u32x4r xf[PF][TWO ? 2 : 3], wf[PF][TWO ? 2 : 3];
-    auto load = [&](int slot, int ks) {
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-        if (pl >= (TWO ? 2 : 3)) continue;
-        xf[slot][pl] = *reinterpret_cast<const u32x4r*>(xp + (size_t)pl * p.hplane + (size_t)ks * 512);
-        wf[slot][pl] = *reinterpret_cast<const u32x4r*>(w0 + (size_t)pl * wplane + (size_t)ks * 512);
-      }
-    };
-    auto step = [&](int slot) {
-      if constexpr (TWO) {     // hi.hi + lo.hi + hi.lo in fp16 (smallest terms first)
-        const f16x8r wh_ = __builtin_bit_cast(f16x8r, wf[slot][0]), wl_ = __builtin_bit_cast(f16x8r, wf[slot][1]);
-        const f16x8r xh_ = __builtin_bit_cast(f16x8r, xf[slot][0]), xl_ = __builtin_bit_cast(f16x8r, xf[slot][1]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl_, wh_, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh_, wl_, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh_, wh_, acc, 0, 0, 0);
-      } else {
-      const bf16x8r bh = __builtin_bit_cast(bf16x8r, wf[slot][0]), bm = __builtin_bit_cast(bf16x8r, wf[slot][1]);
-      const bf16x8r bl = __builtin_bit_cast(bf16x8r, wf[slot][2]);
-      const bf16x8r xh = __builtin_bit_cast(bf16x8r, xf[slot][0]), xm = __builtin_bit_cast(bf16x8r, xf[slot][1]);
-      const bf16x8r xl = __builtin_bit_cast(bf16x8r, xf[slot][2]);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bm, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm, bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bm, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, bh, acc, 0, 0, 0);
-      }
-    };
-    const int nks = kslice / 16;
-#pragma unroll
-    for (int j = 0; j < PF; ++j)
-      if (j < nks) load(j, j);
-    for (int ks = 0; ks < nks; ks += PF) {
-#pragma unroll
-      for (int j = 0; j < PF; ++j)
-        if (ks + j < nks) {
-          step(j);
-          if (ks + j + PF < nks) load(j, ks + j + PF);
-        }
-    }
+    const f32x16r acc = split_contract<TWO, false>(xp, p.hplane, w0, wplane, kslice / 16, true);
 #pragma unroll
     for (int r = 0; r < 16; ++r) red[wave][(r & 3) + 8 * (r >> 2) + 4 * half][l31] = acc[r];
   }
@@ -1376,7 +1246,7 @@ __device__ __forceinline__ void beam2_joint_body(const Beam2P& p, const unsigned
 }
 
 template <int RG, bool TWO>
-__global__ __launch_bounds__(512) void beam2_joint_kernel(Beam2P p, const unsigned short* __restrict__ wpred, const float* __restrict__ enc_p,
+__global__ __launch_bounds__(512) void beam2_joint_kernel(BeamP p, const unsigned short* __restrict__ wpred, const float* __restrict__ enc_p,
                                                           const float* __restrict__ w_out, float* __restrict__ plog, int t, int gemm) {
   __shared__ float red[8][32][33];
   __shared__ float zs[32 * RG][33];
@@ -1388,8 +1258,8 @@ __global__ __launch_bounds__(512) void beam2_joint_kernel(Beam2P p, const unsign
 // read a round later), the joint is and uses a quarter of the CUs -- so the G workgroups (block ids behind the joint's) fill
 // the rest of the chip beside it instead of a launch of their own (19 us per step).  A second stream was measured for this: the
 // event hand-overs between two streams cost 7 .. 25 us of idle each on this chip (profiles/r05k_*), more than G itself.
-template <int RGJ, int RGG, bool TWO>
-__global__ __launch_bounds__(512) void beam2_joint_g_kernel(Beam2P p, const unsigned short* __restrict__ wpred, const float* __restrict__ enc_p,
+template <int RGJ, bool TWO>
+__global__ __launch_bounds__(512) void beam2_joint_g_kernel(BeamP p, const unsigned short* __restrict__ wpred, const float* __restrict__ enc_p,
                                                             const float* __restrict__ w_out, float* __restrict__ plog, int t,
                                                             const unsigned short* __restrict__ whh, int jx, int jy, int gx, int gy,
                                                             int g_layer0) {
@@ -1403,7 +1273,7 @@ __global__ __launch_bounds__(512) void beam2_joint_g_kernel(Beam2P p, const unsi
   }
   id -= jx * jy;
   const int b = id % gx, rb = (id / gx) % gy, l = g_layer0 + id / (gx * gy);      // (the lower layers' G rode with the cell GEMMs)
-  pred_gemm3_body<false, RGG, TWO>(p, whh, l, b, rb, red);
+  pred_gemm3_body<false, 2, TWO>(p, whh, l, b, rb, red);
 }
 
 // The logit of candidate c (row c / V1 of utterance i's w rows, label c % V1): b_out[v] + the J / 32 slices' partial sums, loaded
@@ -1411,7 +1281,7 @@ __global__ __launch_bounds__(512) void beam2_joint_g_kernel(Beam2P p, const unsi
 // added in slice order.  Needs nothing but the launch arguments, so a kernel calls it for c = tid BEFORE it waits for its first
 // loaded word (the live count, the length): the logits' round trip then runs beside that one instead of after it.  Rows past
 // the live count hold stale sums; they are loaded and never used.
-__device__ __forceinline__ float beam2_logit(const Beam2P& p, int i, int c) {
+__device__ __forceinline__ float beam2_logit(const BeamP& p, int i, int c) {
   const int V1 = p.V + 1;
   const int j = c / V1, v = c - j * V1;
   const float* src = p.plog + ((size_t)i * p.w + j) * V1 + v;
@@ -1430,7 +1300,7 @@ __device__ __forceinline__ float beam2_logit(const Beam2P& p, int i, int c) {
 
 // cand[j * V1 + v] = log_softmax_v(logit of (j, v)) for the rows j < rows of utterance i; `cand` in LDS, all 256 threads, ends
 // with a barrier.  `first` = beam2_logit(p, i, tid), loaded by the caller at its top (any value when tid >= w * V1).
-__device__ __forceinline__ void beam2_logp_rows(const Beam2P& p, float* cand, int i, int rows, int tid, float first) {
+__device__ __forceinline__ void beam2_logp_rows(const BeamP& p, float* cand, int i, int rows, int tid, float first) {
   const int V1 = p.V + 1, lane = tid & 63, wave = tid >> 6;
   if (tid < rows * V1) cand[tid] = first;
   for (int c = tid + 256; c < rows * V1; c += 256) cand[c] = beam2_logit(p, i, c);
@@ -1449,68 +1319,9 @@ __device__ __forceinline__ void beam2_logp_rows(const Beam2P& p, float* cand, in
   __syncthreads();
 }
 
-// blank transitions of one round into the LDS copy of B (beam_round_kernel's merge); returns the new count through wi[0].
-// All 256 threads; b_* hold B (bc0 entries), old_* the live hypotheses (cnt), cand their log-probabilities.
-__device__ __forceinline__ void beam2_blank_merge(int cnt, int bc0, int bcap, int V1, int blank, const float* cand, const int* old_node,
-                                                  const int* old_slot, const float* old_score, int* b_node, int* b_slot,
-                                                  float* b_score, int* match_at, int* wi, int tid) {
-  const int lane = tid & 63, wave = tid >> 6;
-  if (tid < 32) match_at[tid] = -1;
-  __syncthreads();
-  for (int idx = tid; idx < cnt * bc0; idx += 256) {
-    const int j = idx / bc0, b = idx - j * bc0;
-    if (b_node[b] == old_node[j]) match_at[j] = b;
-  }
-  __syncthreads();
-  if (wave == 0) {
-    const int j = lane;
-    bool dup = false;
-    if (j < cnt)
-      for (int k = 0; k < j; ++k) dup |= old_node[k] == old_node[j];
-    if (__any(dup)) {
-      if (lane == 0) {
-        int bc = bc0;
-        for (int jj = 0; jj < cnt; ++jj) {
-          const float s = old_score[jj] + cand[jj * V1 + blank];
-          int at = -1;
-          for (int b = 0; b < bc; ++b)
-            if (b_node[b] == old_node[jj]) { at = b; break; }
-          if (at >= 0) {
-            b_score[at] = logaddexp32(b_score[at], s);
-          } else if (bc < bcap) {
-            b_node[bc] = old_node[jj];
-            b_score[bc] = s;
-            b_slot[bc] = old_slot[jj];
-            ++bc;
-          }
-        }
-        wi[0] = bc;
-      }
-    } else {
-      const bool have = j < cnt;
-      const int at = have ? match_at[j] : 0;
-      const bool unmatched = have && at < 0;
-      const unsigned long long um = __ballot(unmatched);
-      const int pos = bc0 + __popcll(um & ((1ull << lane) - 1ull));
-      if (have) {
-        const float s = old_score[j] + cand[j * V1 + blank];
-        if (at >= 0) {
-          b_score[at] = logaddexp32(b_score[at], s);
-        } else if (pos < bcap) {
-          b_node[pos] = old_node[j];
-          b_score[pos] = s;
-          b_slot[pos] = old_slot[j];
-        }
-      }
-      if (lane == 0) wi[0] = min(bc0 + (int)__popcll(um), bcap);
-    }
-  }
-  __syncthreads();
-}
-
 // One emission round that is not the frame's last: beam_round_kernel with the log-probabilities made from the joint kernel's
 // partial sums.
-__global__ __launch_bounds__(256) void beam2_round_kernel(Beam2P p, int t, int region, int first) {
+__global__ __launch_bounds__(256) void beam2_round_kernel(BeamP p, int t, int region, int first) {
   extern __shared__ __attribute__((aligned(16))) float cand[];  // [w * V1] log-probabilities, then candidate scores
   __shared__ int wi[4];
   __shared__ int pick_idx[32];
@@ -1521,7 +1332,7 @@ __global__ __launch_bounds__(256) void beam2_round_kernel(Beam2P p, int t, int r
   __shared__ float b_score[128];
   __shared__ int n_pick, next_node;
   __shared__ int match_at[32];
-  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.x, tid = threadIdx.x;
   const int w = p.w, V1 = p.V + 1, blank = p.V;
   // every load of the kernel's top is issued before the first loaded word is used: the sets' entries into registers, then the
   // logits, and only then the LDS copies (which wait)
@@ -1545,7 +1356,7 @@ __global__ __launch_bounds__(256) void beam2_round_kernel(Beam2P p, int t, int r
   if (t >= len_i) return;
   if (tid == 0) { n_pick = 0; next_node = nodes0; }
   beam2_logp_rows(p, cand, i, cnt, tid, logit0);
-  beam2_blank_merge(cnt, bc0, p.bcap, V1, blank, cand, old_node, old_slot, old_score, b_node, b_slot, b_score, match_at, wi, tid);
+  beam_blank_merge(cnt, bc0, p.bcap, V1, blank, cand, old_node, old_slot, old_score, b_node, b_slot, b_score, match_at, wi, tid);
   {
     const int bc = wi[0];
     if (tid == 0) p.B_cnt[i] = bc;
@@ -1556,67 +1367,7 @@ __global__ __launch_bounds__(256) void beam2_round_kernel(Beam2P p, int t, int r
     }
   }
   __syncthreads();
-  // label extensions: the w best of cnt * V1 candidates (score desc, ties -> lowest flat index), blank and
-  // non-finite scores excluded
-  const int C = cnt * V1;
-  for (int c = tid; c < C; c += 256) {
-    const int j = c / V1, k = c - j * V1;
-    const float s = old_score[j] + cand[c];
-    cand[c] = (k == blank || !isfinite(s)) ? -INFINITY : s;
-  }
-  __syncthreads();
-  if (wave == 0) {
-    int npk = 0;
-    for (int q = 0; q < w; ++q) {
-      float bv = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int c = lane; c < C; c += 64) {
-        const float v = cand[c];
-        if (v > bv) { bv = v; bi = c; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-      }
-      if (bi == 0x7fffffff || !(bv > -INFINITY)) break;      // wave-uniform: nothing finite is left
-      if (lane == 0) {
-        pick_idx[npk] = bi;
-        pick_val[npk] = bv;
-        cand[bi] = -INFINITY;
-      }
-      ++npk;
-    }
-    if (lane == 0) n_pick = npk;
-  }
-  __syncthreads();
-  const int np = n_pick;
-  if (tid < np) {
-    const int q = tid;
-    const int hi = pick_idx[q] / V1, k = pick_idx[q] - hi * V1;
-    const int parent = old_node[hi];
-    int32_t* ch = p.child + ((size_t)i * p.maxn + parent) * p.V + k;
-    int node = *ch;
-    if (node < 0) {
-      node = atomicAdd(&next_node, 1);
-      if (node < p.maxn) {
-        p.node_parent[(size_t)i * p.maxn + node] = parent;
-        p.node_label[(size_t)i * p.maxn + node] = k;
-        *ch = node;
-      } else {
-        node = parent;  // cannot happen: maxn bounds every possible insertion
-      }
-    }
-    const int slot = region * p.R + i * w + q;
-    p.A_node[i * w + q] = node;
-    p.A_score[i * w + q] = pick_val[q];
-    p.A_slot[i * w + q] = slot;
-    p.ext_label[i * w + q] = k;
-    p.ext_src[i * w + q] = old_slot[hi];
-    p.ext_dst[i * w + q] = slot;
-  }
-  __syncthreads();
+  const int np = beam_extend(p, i, cnt, region, cand, old_node, old_slot, old_score, pick_idx, pick_val, &n_pick, &next_node, tid);
   if (tid == 0) {
     p.A_cnt[i] = np;
     p.node_cnt[i] = min(next_node, p.maxn);
@@ -1626,7 +1377,7 @@ __global__ __launch_bounds__(256) void beam2_round_kernel(Beam2P p, int t, int r
 // The frame's last round (blank transitions only) and the frame end in one kernel, grid (w, N): every workgroup repeats the
 // (cheap, LDS) merge and selection and moves ONE survivor's state -- h, c, G of every layer and the projected predictor
 // output -- into frame-start region (t + 1) & 1.
-__global__ __launch_bounds__(256) void beam2_frame_end_kernel(Beam2P p, int t, int first) {
+__global__ __launch_bounds__(256) void beam2_frame_end_kernel(BeamP p, int t, int first) {
   extern __shared__ __attribute__((aligned(16))) float cand[];
   __shared__ int wi[4];
   __shared__ int old_node[32], old_slot[32];
@@ -1666,42 +1417,8 @@ __global__ __launch_bounds__(256) void beam2_frame_end_kernel(Beam2P p, int t, i
     return;
   }
   beam2_logp_rows(p, cand, i, cnt, tid, logit0);
-  beam2_blank_merge(cnt, bc0, p.bcap, V1, blank, cand, old_node, old_slot, old_score, b_node, b_slot, b_score, match_at, wi, tid);
-  const int bc = wi[0];
-  // the beam_width best of B, one after the other (first maximum = earliest arrival among equals), by ONE wave
-  if (tid < 64) {
-    const int lane = tid;
-    const float s0 = lane < bc ? b_score[lane] : 0.f, s1 = lane + 64 < bc ? b_score[lane + 64] : 0.f;
-    bool t0 = !(lane < bc), t1 = !(lane + 64 < bc);          // "taken" also stands for "does not exist"
-    int ns = 0;
-    for (int x = 0; x < w && x < bc; ++x) {
-      bool have = false;
-      float bv = 0.f;
-      int bi = 0x7fffffff;
-      if (!t0) { have = true; bv = s0; bi = lane; }
-      if (!t1 && (!have || s1 > bv)) { have = true; bv = s1; bi = lane + 64; }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const bool oh = __shfl_xor((int)have, o, 64) != 0;
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        const bool take = oh && (!have || ov > bv || (!(bv > ov) && oi < bi));
-        if (take) { have = true; bv = ov; bi = oi; }
-      }
-      if (!have) break;                                       // wave-uniform
-      if (bi == lane) t0 = true;
-      if (bi == lane + 64) t1 = true;
-      if (lane == 0) {
-        sel_src[ns] = b_slot[bi];
-        sel_node[ns] = b_node[bi];
-        sel_score[ns] = b_score[bi];
-      }
-      ++ns;
-    }
-    if (lane == 0) n_sel = ns;
-  }
-  __syncthreads();
-  const int ns = n_sel;
+  beam_blank_merge(cnt, bc0, p.bcap, V1, blank, cand, old_node, old_slot, old_score, b_node, b_slot, b_score, match_at, wi, tid);
+  const int ns = beam_select(wi[0], w, b_node, b_slot, b_score, sel_src, sel_node, sel_score, &n_sel, tid);
   if (q == 0 && tid == 0) p.nA_cnt[i] = ns;
   if (q >= ns) return;
   const size_t src = (size_t)sel_src[q], dst = (size_t)((t + 1) & 1) * p.R + i * w + q;
@@ -1749,37 +1466,22 @@ __global__ __launch_bounds__(256) void beam2_frame_end_kernel(Beam2P p, int t, i
 
 struct Net {
   const float* embedding;
+  const float* const* w_ih;
+  const float* const* w_hh;
+  const float* const* b_ih;
+  const float* const* b_hh;
   const float* w_pred;
   const float* w_out;
   const float* b_out;
   int V, D, H, L, J;
-  int fused;     // one launch per predictor layer (pred_layer_fused_kernel): unit-major weight planes
+  // predictor_step()'s form, one for all layers of a call: every layer has K % 128 == 0 (K slices of whole 16-deep k-steps
+  // for eight waves) and H % 16 == 0 -> split weight planes and one launch per layer (pred_layer_fused_kernel); anything else
+  // -> the exact-f32 path (pack_cat_kernel, linear_splitk_launch, lstm_cell_kernel)
+  int fused;
 };
 
 // One prediction-network step for the R request rows described by ext_label / ext_src / ext_dst.
 // The pred_proj GEMM leaves its K-slice partial sums in pp_tmp; joint_slots_kernel adds and commits them.
-// the split form needs K slices of whole 16-deep k-steps and whole 64-column tiles; all layers of a call take the same path
-// K slices of the split form: MS_RNNT_GATES_KSPLIT (2, 4 or 8); default 4 -- 64 column tiles x 4 slices = 256 workgroups of 8 waves,
-// and half the partial sums for the cell kernel to add (measured 111 .. 114 ms per decode against 114 .. 119 with 8)
-int gates_split_slices() {
-  static const int v = [] {
-    const char* e = getenv("MS_RNNT_GATES_KSPLIT");
-    const int k = e ? atoi(e) : 4;
-    return (k == 2 || k == 4 || k == 8) ? k : 4;
-  }();
-  return v;
-}
-bool gates_split_ok(const Net& n, int l) {
-  static const bool off = getenv("MS_RNNT_GATES_F32") && getenv("MS_RNNT_GATES_F32")[0] == '1';
-  if (off) return false;
-  for (int i = 0; i < n.L; ++i) {
-    const int K = (i == 0 ? n.D : n.H) + n.H;
-    if (K % (16 * KSPLIT) != 0 || (4 * n.H) % 64 != 0) return false;
-  }
-  (void)l;
-  return true;
-}
-
 int predictor_step(const Net& n, const DecLayout& W, char* ws, hipStream_t s) {
   const int R = W.R, H = n.H, L = n.L;
   int32_t* ext_label = (int32_t*)(ws + W.ext_label);
@@ -1790,176 +1492,120 @@ int predictor_step(const Net& n, const DecLayout& W, char* ws, hipStream_t s) {
   float* xrow = (float*)(ws + W.xrow);
   float* gates = (float*)(ws + W.gates);
   float* htop = (float*)(ws + W.htop);
-  const int frag = gates_split_ok(n, 0) ? 1 : 0;
   const size_t xplane = (size_t)((R + 31) / 32 * 32) * ((n.D > H ? n.D : H) + H);   // elements between the three x planes
   hipLaunchKernelGGL(pred_gather_kernel, dim3(R), dim3(256), 0, s, n.embedding, ext_label, ext_src, ext_dst, st_h, xrow, n.D,
-                     H, L, n.V + 1, frag, xplane);
+                     H, L, n.V + 1, n.fused, xplane);
   MS_LAUNCH_CHECK();
   for (int l = 0; l < L; ++l) {
     const int K = (l == 0 ? n.D : H) + H;
-    int nsplit = KSPLIT;
+    const float* bias = (const float*)(ws + W.bcat) + W.bcat_off[l];
     if (n.fused) {
+      // three bf16 planes of [W_ih | W_hh] (pack_cat3_kernel), layer l at 3 x wcat_off[l] elements of 2 bytes
       const unsigned short* planes = (const unsigned short*)(ws + W.wcat) + 3 * W.wcat_off[l];
       const unsigned short* xin = reinterpret_cast<const unsigned short*>(ws + ((l & 1) ? W.xrow2 : W.xrow));
       unsigned short* xout = reinterpret_cast<unsigned short*>(ws + ((l & 1) ? W.xrow : W.xrow2));
-      const float* bias = (const float*)(ws + W.bcat) + W.bcat_off[l];
       if (R > 32)
         hipLaunchKernelGGL(pred_layer_fused_kernel<2>, dim3(H / 8, (R + 63) / 64), dim3(512), 0, s, xin, xplane, planes, bias, ext_src,
                            ext_dst, st_h, st_c, xout, htop, R, K, H, L, l);
       else
         hipLaunchKernelGGL(pred_layer_fused_kernel<1>, dim3(H / 8, 1), dim3(512), 0, s, xin, xplane, planes, bias, ext_src, ext_dst,
                            st_h, st_c, xout, htop, R, K, H, L, l);
-      MS_LAUNCH_CHECK();
-      continue;
-    }
-    if (gates_split_ok(n, l)) {
-      // three bf16 planes of [W_ih | W_hh] (pack_cat3_kernel), plane l at 3 x wcat_off[l] elements of 2 bytes
-      nsplit = gates_split_slices();
-      const unsigned short* planes = (const unsigned short*)(ws + W.wcat) + 3 * W.wcat_off[l];
-      hipLaunchKernelGGL(pred_gates_split_kernel, dim3(4 * H / 64, nsplit, (R + 127) / 128), dim3(512), 0, s, reinterpret_cast<const unsigned short*>(xrow), xplane, planes,
-                         (const float*)(ws + W.bcat) + W.bcat_off[l], gates, R, K, 4 * H, nsplit);
-      MS_LAUNCH_CHECK();
     } else {
-      int rc = ms::linear_splitk_launch(xrow, (const float*)(ws + W.wcat) + W.wcat_off[l],
-                                        (const float*)(ws + W.bcat) + W.bcat_off[l], gates, R, K, 4 * H, KSPLIT, s);
+      int rc = ms::linear_splitk_launch(xrow, (const float*)(ws + W.wcat) + W.wcat_off[l], bias, gates, R, K, 4 * H, KSPLIT, s);
       if (rc != MS_OK) return rc;
+      hipLaunchKernelGGL(lstm_cell_kernel, dim3(R), dim3(256), 0, s, gates, ext_src, ext_dst, st_h, st_c, xrow, htop, H, L, l, R);
     }
-    hipLaunchKernelGGL(lstm_cell_kernel, dim3(R), dim3(256), 0, s, gates, ext_src, ext_dst, st_h, st_c, xrow, htop, H, L, l,
-                       R, nsplit, frag, xplane);
     MS_LAUNCH_CHECK();
   }
   return ms::linear_splitk_launch(htop, n.w_pred, nullptr, (float*)(ws + W.pp_tmp), R, H, n.J, KSPLIT, s);
 }
 
-// The round-5 beam decode (see pred_gemm3_kernel): the same hypothesis lists, trie and pool as the round-4 sequence below it.
-int beam2_decode(const BeamP& bp, const DecLayout& W, char* ws, const float* embedding, const float* const* w_ih,
-                 const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, const float* w_pred,
-                 const float* w_out, const float* b_out, const float* enc_p, int32_t* out_idx, int32_t* out_len, float* out_score,
-                 int T, int N, int V, int D, int H, int L, int J, int w, int max_symbols, hipStream_t s) {
-  const int R = W.R, V1 = V + 1;
-  const size_t rpad = (size_t)((R + 63) / 64 * 64);
-  Beam2P q{};
-  {
-    const char* e = getenv("MS_RNNT_PLANES");      // 3 = the exact three-bf16 operands of round 5 (A/B runs); default: two fp16 planes
-    q.two = (e && e[0] == '3') ? 0 : 1;
-  }
-  q.lens = bp.lens;
-  int32_t* a2 = (int32_t*)(ws + W.v2_A2);
-  int32_t* Acnt[2] = {bp.A_cnt, a2};
-  int32_t* Anode[2] = {bp.A_node, a2 + N};
-  float* Ascore[2] = {bp.A_score, (float*)(a2 + N + R)};
-  int32_t* Aslot[2] = {bp.A_slot, a2 + N + 2 * R};
-  q.B_cnt = bp.B_cnt; q.B_node = bp.B_node; q.B_slot = bp.B_slot; q.B_score = bp.B_score;
-  q.ext_label = bp.ext_label; q.ext_src = bp.ext_src; q.ext_dst = bp.ext_dst;
-  q.node_cnt = bp.node_cnt; q.node_parent = bp.node_parent; q.node_label = bp.node_label; q.child = bp.child;
-  q.st_h = (float*)(ws + W.st_h); q.st_c = (float*)(ws + W.st_c); q.pp = (float*)(ws + W.pp); q.G = (float*)(ws + W.v2_G);
-  q.E = (const float*)(ws + W.v2_E); q.bias = (const float*)(ws + W.v2_bias); q.plog = (const float*)(ws + W.v2_plog); q.b_out = b_out;
-  q.hpl = (unsigned short*)(ws + W.v2_hpl); q.hplane = rpad * H;
-  q.N = N; q.w = w; q.V = V; q.bcap = bp.bcap; q.maxn = bp.maxn; q.R = R; q.H = H; q.L = L; q.J = J; q.NS = J / 32;
-  auto set_frame = [&](int t) {
-    const int c = t & 1, n = c ^ 1;
-    q.A_cnt = Acnt[c]; q.A_node = Anode[c]; q.A_score = Ascore[c]; q.A_slot = Aslot[c];
-    q.nA_cnt = Acnt[n]; q.nA_node = Anode[n]; q.nA_score = Ascore[n]; q.nA_slot = Aslot[n];
-  };
-  set_frame(0);
-  unsigned short* whh = (unsigned short*)(ws + W.v2_whh);
-  unsigned short* wih = (unsigned short*)(ws + W.v2_wih);
-  unsigned short* wpred = (unsigned short*)(ws + W.v2_wpred);
+// The frames of the re-cut beam sequence.  RGJ = 32-row groups per joint workgroup: one (eight K slices) where H % 128 == 0 --
+// 64 workgroups instead of 32 at configs[3] --, else two; the gate GEMMs always take two (64 rows, four K slices; measured: 11.7
+// against 14.1 us per layer).
+template <int RGJ, bool TWO>
+int beam2_frames(BeamP p, const Net& n, const DecLayout& W, char* ws, const float* enc_p, int32_t* out_idx, int32_t* out_len,
+                 float* out_score, int T, int max_symbols, hipStream_t s) {
+  const int R = W.R, N = p.N, w = p.w, V1 = n.V + 1, L = n.L;
+  const unsigned short* whh = (const unsigned short*)(ws + W.v2_whh);
+  const unsigned short* wih = (const unsigned short*)(ws + W.v2_wih);
+  const unsigned short* wpred = (const unsigned short*)(ws + W.v2_wpred);
   float* plog = (float*)(ws + W.v2_plog);
-  // ---- once per call: the operand planes, the embedding table, the biases
-  const size_t wplane3 = (size_t)3 * 4 * H * H;
-  for (int l = 0; l < L; ++l) {
-    hipLaunchKernelGGL(pack_rows3_kernel, dim3(4 * H), dim3(256), 0, s, w_hh[l], whh + (size_t)l * wplane3, 4 * H, H, H, q.two);
-    if (l > 0) {
-      hipLaunchKernelGGL(pack_rows3_kernel, dim3(4 * H), dim3(256), 0, s, w_ih[l], wih + (size_t)(l - 1) * wplane3, 4 * H, H, H, q.two);
-      hipLaunchKernelGGL(unit_major_add_kernel, dim3(ms::cdiv(4 * H, 256)), dim3(256), 0, s, (const float*)nullptr, b_ih[l], b_hh[l],
-                         (float*)(ws + W.v2_bias) + (size_t)l * 4 * H, H, 0);
-    }
-  }
-  hipLaunchKernelGGL(pack_rows3_kernel, dim3(J), dim3(256), 0, s, w_pred, wpred, J, H, 0, q.two);
-  MS_LAUNCH_CHECK();
-  int rc = ms::linear_launch(embedding, w_ih[0], nullptr, (float*)(ws + W.v2_Etmp), V1, D, 4 * H, MS_ACT_NONE, 0.f, 0.f, s);
-  if (rc != MS_OK) return rc;
-  hipLaunchKernelGGL(unit_major_add_kernel, dim3(ms::cdiv(4 * H, 256)), dim3(256), 0, s, (const float*)(ws + W.v2_Etmp), b_ih[0],
-                     b_hh[0], (float*)(ws + W.v2_E), H, V1);
-  MS_LAUNCH_CHECK();
-  // rows per workgroup: 32 (eight K slices) for the joint -- 64 workgroups instead of 32 at configs[3] --, 64 (four K slices) for
-  // the gate GEMMs (measured: 11.7 against 14.1 us per layer; MS_RNNT_RG = 1 / 2 forces one form for both)
-  static const int rg_env = getenv("MS_RNNT_RG") ? atoi(getenv("MS_RNNT_RG")) : 0;
-  const int rgg = rg_env == 1 && H % 128 == 0 ? 1 : 2;
-  const int rgj = rg_env == 2 || H % 128 != 0 ? 2 : 1;
-  const dim3 ggrid(H / 8, (R + 32 * rgg - 1) / (32 * rgg));
-  const dim3 jgrid(J / 32, (R + 32 * rgj - 1) / (32 * rgj));
+  const dim3 ggrid(n.H / 8, (R + 63) / 64);
+  const dim3 jgrid(n.J / 32, (R + 32 * RGJ - 1) / (32 * RGJ));
+  const int nj = jgrid.x * jgrid.y, ng = ggrid.x * ggrid.y;
   const size_t cand_lds = (size_t)w * V1 * 4, wo_lds = (size_t)V1 * 32 * 4;
-  // (MS_RNNT_FUSE_G=0, read per call: the lower layers' G in the joint's launch as in round 5 -- A/B runs)
-  const char* fg = getenv("MS_RNNT_FUSE_G");
-  const bool fuse_g = !(fg && fg[0] == '0') && L > 1;
-  auto predictor_step2 = [&]() {       // cell 0 of the request rows, then cells 1 .. L - 1; G rides with the step's joint launch
-    hipLaunchKernelGGL(beam2_cell0_kernel, dim3(R), dim3(256), 0, s, q);
-    for (int l = 1; l < L; ++l) {
-      if (fuse_g) {
-        const dim3 cg(ggrid.x, ggrid.y, 2);
-#define MS_CG(RG_) \
-        if (q.two) hipLaunchKernelGGL((pred_gemm3_cell_g_kernel<RG_, true>), cg, dim3(512), 0, s, q, (const unsigned short*)wih, (const unsigned short*)whh, l); \
-        else hipLaunchKernelGGL((pred_gemm3_cell_g_kernel<RG_, false>), cg, dim3(512), 0, s, q, (const unsigned short*)wih, (const unsigned short*)whh, l)
-        if (rgg == 1) { MS_CG(1); } else { MS_CG(2); }
-#undef MS_CG
-      } else if (rgg == 1) {
-        if (q.two) hipLaunchKernelGGL((pred_gemm3_kernel<true, 1, true>), ggrid, dim3(512), 0, s, q, (const unsigned short*)wih, l);
-        else hipLaunchKernelGGL((pred_gemm3_kernel<true, 1, false>), ggrid, dim3(512), 0, s, q, (const unsigned short*)wih, l);
-      } else {
-        if (q.two) hipLaunchKernelGGL((pred_gemm3_kernel<true, 2, true>), ggrid, dim3(512), 0, s, q, (const unsigned short*)wih, l);
-        else hipLaunchKernelGGL((pred_gemm3_kernel<true, 2, false>), ggrid, dim3(512), 0, s, q, (const unsigned short*)wih, l);
-      }
-    }
+  // cell 0 of the request rows, then cell l beside G of layer l - 1; the top layer's G rides with the step's joint launch
+  auto predictor_step2 = [&]() {
+    hipLaunchKernelGGL(beam2_cell0_kernel, dim3(R), dim3(256), 0, s, p);
+    for (int l = 1; l < L; ++l)
+      hipLaunchKernelGGL((pred_gemm3_cell_g_kernel<2, TWO>), dim3(ggrid.x, ggrid.y, 2), dim3(512), 0, s, p, wih, whh, l);
   };
   auto joint = [&](int t, bool after_step) {
-    const int g_layer0 = fuse_g ? L - 1 : 0;
-    const int nj = jgrid.x * jgrid.y, ng = ggrid.x * ggrid.y * (L - g_layer0);
-    if (after_step) {
-      // the step's new states: their projected predictor output (joint) and their G (beside it)
-#define MS_JG(RJ, RGm) do { if (q.two) MS_JG2(RJ, RGm, true); else MS_JG2(RJ, RGm, false); } while (0)
-#define MS_JG2(RJ, RGm, TW) hipLaunchKernelGGL((beam2_joint_g_kernel<RJ, RGm, TW>), dim3(nj + ng), dim3(512), wo_lds, s, q, (const unsigned short*)wpred, \
-                                          enc_p, w_out, plog, t, (const unsigned short*)whh, (int)jgrid.x, (int)jgrid.y, (int)ggrid.x, (int)ggrid.y, g_layer0)
-      if (rgj == 1 && rgg == 1) MS_JG(1, 1);
-      else if (rgj == 1) MS_JG(1, 2);
-      else if (rgg == 1) MS_JG(2, 1);
-      else MS_JG(2, 2);
-#undef MS_JG
-#undef MS_JG2
-    } else if (rgj == 1) {
-      if (q.two) hipLaunchKernelGGL((beam2_joint_kernel<1, true>), jgrid, dim3(512), wo_lds, s, q, (const unsigned short*)wpred, enc_p, w_out, plog, t, 0);
-      else hipLaunchKernelGGL((beam2_joint_kernel<1, false>), jgrid, dim3(512), wo_lds, s, q, (const unsigned short*)wpred, enc_p, w_out, plog, t, 0);
-    } else {
-      if (q.two) hipLaunchKernelGGL((beam2_joint_kernel<2, true>), jgrid, dim3(512), wo_lds, s, q, (const unsigned short*)wpred, enc_p, w_out, plog, t, 0);
-      else hipLaunchKernelGGL((beam2_joint_kernel<2, false>), jgrid, dim3(512), wo_lds, s, q, (const unsigned short*)wpred, enc_p, w_out, plog, t, 0);
-    }
+    if (after_step)      // the step's new states: their projected predictor output (joint) and their top layer's G (beside it)
+      hipLaunchKernelGGL((beam2_joint_g_kernel<RGJ, TWO>), dim3(nj + ng), dim3(512), wo_lds, s, p, wpred, enc_p, n.w_out, plog, t, whh,
+                         (int)jgrid.x, (int)jgrid.y, (int)ggrid.x, (int)ggrid.y, L - 1);
+    else
+      hipLaunchKernelGGL((beam2_joint_kernel<RGJ, TWO>), jgrid, dim3(512), wo_lds, s, p, wpred, enc_p, n.w_out, plog, t, 0);
+  };
+  auto next_frame = [&]() {            // the frame end wrote the next frame's live set into the other buffer
+    std::swap(p.A_cnt, p.nA_cnt);
+    std::swap(p.A_node, p.nA_node);
+    std::swap(p.A_score, p.nA_score);
+    std::swap(p.A_slot, p.nA_slot);
   };
   // ---- the root hypotheses' predictor state (blank on the zero state)
   predictor_step2();
   MS_LAUNCH_CHECK();
   for (int t = 0; t < T; ++t) {
-    set_frame(t);
     for (int v = 0; v < max_symbols; ++v) {
       const int last = v == max_symbols - 1;
       // the rows' states are new after a predictor step (and at the very start); a frame's first round works on the survivors
       joint(t, v > 0 || t == 0);
       if (last) {
-        hipLaunchKernelGGL(beam2_frame_end_kernel, dim3(w, N), dim3(256), cand_lds, s, q, t, v == 0 ? 1 : 0);
+        hipLaunchKernelGGL(beam2_frame_end_kernel, dim3(w, N), dim3(256), cand_lds, s, p, t, v == 0 ? 1 : 0);
       } else {
-        hipLaunchKernelGGL(beam2_round_kernel, dim3(N), dim3(256), cand_lds, s, q, t, 2 + v, v == 0 ? 1 : 0);
+        hipLaunchKernelGGL(beam2_round_kernel, dim3(N), dim3(256), cand_lds, s, p, t, 2 + v, v == 0 ? 1 : 0);
         predictor_step2();
       }
       MS_LAUNCH_CHECK();
     }
+    next_frame();
   }
-  set_frame(T);           // the last frame end wrote buffer T & 1
-  BeamP fin = bp;
-  fin.A_cnt = q.A_cnt; fin.A_node = q.A_node; fin.A_score = q.A_score; fin.A_slot = q.A_slot;
-  hipLaunchKernelGGL(beam_finish_kernel, dim3(N), dim3(64), 0, s, fin, out_idx, out_len, out_score,
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(N), dim3(64), 0, s, p, out_idx, out_len, out_score,
                      T * (max_symbols > 1 ? max_symbols - 1 : 0) + 1);
   MS_LAUNCH_CHECK();
   return MS_OK;
+}
+
+// The re-cut beam decode (see the comment above pack_rows3_kernel): the same hypothesis lists, trie and pool as the round-4
+// sequence in ms_rnnt_decode.  Once per call the operand planes, the embedding table and the biases; then the frames.
+int beam2_decode(const BeamP& p, const Net& n, const DecLayout& W, char* ws, const float* enc_p, int32_t* out_idx, int32_t* out_len,
+                 float* out_score, int T, int max_symbols, hipStream_t s) {
+  const int V1 = n.V + 1, H = n.H, L = n.L, J = n.J;
+  unsigned short* whh = (unsigned short*)(ws + W.v2_whh);
+  unsigned short* wih = (unsigned short*)(ws + W.v2_wih);
+  const size_t wplane3 = (size_t)3 * 4 * H * H;
+  for (int l = 0; l < L; ++l) {
+    hipLaunchKernelGGL(pack_rows3_kernel, dim3(4 * H), dim3(256), 0, s, n.w_hh[l], whh + (size_t)l * wplane3, 4 * H, H, H, p.two);
+    if (l > 0) {
+      hipLaunchKernelGGL(pack_rows3_kernel, dim3(4 * H), dim3(256), 0, s, n.w_ih[l], wih + (size_t)(l - 1) * wplane3, 4 * H, H, H, p.two);
+      hipLaunchKernelGGL(unit_major_add_kernel, dim3(ms::cdiv(4 * H, 256)), dim3(256), 0, s, (const float*)nullptr, n.b_ih[l], n.b_hh[l],
+                         (float*)(ws + W.v2_bias) + (size_t)l * 4 * H, H, 0);
+    }
+  }
+  hipLaunchKernelGGL(pack_rows3_kernel, dim3(J), dim3(256), 0, s, n.w_pred, (unsigned short*)(ws + W.v2_wpred), J, H, 0, p.two);
+  MS_LAUNCH_CHECK();
+  int rc = ms::linear_launch(n.embedding, n.w_ih[0], nullptr, (float*)(ws + W.v2_Etmp), V1, n.D, 4 * H, MS_ACT_NONE, 0.f, 0.f, s);
+  if (rc != MS_OK) return rc;
+  hipLaunchKernelGGL(unit_major_add_kernel, dim3(ms::cdiv(4 * H, 256)), dim3(256), 0, s, (const float*)(ws + W.v2_Etmp), n.b_ih[0],
+                     n.b_hh[0], (float*)(ws + W.v2_E), H, V1);
+  MS_LAUNCH_CHECK();
+  if (H % 128 == 0)
+    return p.two ? beam2_frames<1, true>(p, n, W, ws, enc_p, out_idx, out_len, out_score, T, max_symbols, s)
+                 : beam2_frames<1, false>(p, n, W, ws, enc_p, out_idx, out_len, out_score, T, max_symbols, s);
+  return p.two ? beam2_frames<2, true>(p, n, W, ws, enc_p, out_idx, out_len, out_score, T, max_symbols, s)
+               : beam2_frames<2, false>(p, n, W, ws, enc_p, out_idx, out_len, out_score, T, max_symbols, s);
 }
 
 }  // namespace
@@ -1990,22 +1636,14 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   const int R = W.R;
-  Net net{embedding, w_pred, w_out, b_out, V, D, H, L, J, 0};
-  {
-    // one launch per predictor layer where the shapes allow it (K slices of whole 16-deep k-steps for eight waves, eight
-    // units per workgroup); MS_RNNT_FUSED=0 (read per call: the tests' A/B switch) keeps gate GEMM + cell kernel
-    const char* e = getenv("MS_RNNT_FUSED");
-    bool ok = !(e && e[0] == '0') && gates_split_ok(net, 0) && H % 8 == 0;
-    for (int l = 0; l < L && ok; ++l) ok = (((l == 0 ? D : H) + H) % 128) == 0;
-    net.fused = ok ? 1 : 0;
-  }
+  Net net{embedding, w_ih, w_hh, b_ih, b_hh, w_pred, w_out, b_out, V, D, H, L, J, H % 16 == 0};
+  for (int l = 0; l < L; ++l) net.fused = net.fused && ((l == 0 ? D : H) + H) % 128 == 0;
 
   for (int l = 0; l < L; ++l) {
     MS_REQUIRE(w_ih[l] && w_hh[l], "null layer weights");
-    if (gates_split_ok(net, l))
+    if (net.fused)
       hipLaunchKernelGGL(pack_cat3_kernel, dim3(4 * H), dim3(256), 0, s, w_ih[l], w_hh[l], b_ih[l], b_hh[l],
-                         (unsigned short*)(ws + W.wcat) + 3 * W.wcat_off[l], (float*)(ws + W.bcat) + W.bcat_off[l], H, l == 0 ? D : H,
-                         net.fused);
+                         (unsigned short*)(ws + W.wcat) + 3 * W.wcat_off[l], (float*)(ws + W.bcat) + W.bcat_off[l], H, l == 0 ? D : H);
     else
       hipLaunchKernelGGL(pack_cat_kernel, dim3(4 * H), dim3(256), 0, s, w_ih[l], w_hh[l], b_ih[l], b_hh[l],
                          (float*)(ws + W.wcat) + W.wcat_off[l], (float*)(ws + W.bcat) + W.bcat_off[l], H, l == 0 ? D : H);
@@ -2043,7 +1681,6 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
     hipEvent_t* ev = poll->ev;
     constexpr int RING = GreedyPoll::RING;
     for (int k = 0; k < RING; ++k) host_done[k] = 0;      // no copy of an earlier call is in flight: every call ends on its last event
-    bool polled = true;
     int last_slot = -1;
     long checks = 0;
     rc = MS_OK;
@@ -2055,7 +1692,7 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
                          max_symbols);
       if (hipGetLastError() != hipSuccess) { ms::set_error("ms_rnnt_decode: launch failed"); rc = MS_ERR_HIP; break; }
       rc = predictor_step(net, W, ws, s);
-      if (rc != MS_OK || !polled || (it + 1) % CHECK_EVERY != 0) continue;
+      if (rc != MS_OK || (it + 1) % CHECK_EVERY != 0) continue;
       // fetch the counter behind this iteration; look at the one fetched two checks ago (already complete, or nearly):
       // the queue stays at least CHECK_EVERY iterations deep and at most 2 * CHECK_EVERY iterations run past the end
       const int slot = (int)(checks % RING);
@@ -2072,17 +1709,20 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
     // the pinned words are targets of copies in flight: wait for the last one (the host has run at most 2 * CHECK_EVERY
     // iterations ahead, so this is short); the ring and the events stay with the thread for its next call
     if (last_slot >= 0) (void)hipEventSynchronize(ev[last_slot]);
-    (void)polled;
     return rc;
   }
 
-  BeamP p;
+  BeamP p{};
   p.lens = lens;
-  p.logp = logp;
   p.A_cnt = A_cnt;
   p.A_node = (int32_t*)(ws + W.A_node);
   p.A_slot = A_slot;
   p.A_score = (float*)(ws + W.A_score);
+  int32_t* a2 = (int32_t*)(ws + W.v2_A2);                // the re-cut sequence's second live set: cnt[N], node, score, slot[R]
+  p.nA_cnt = a2;
+  p.nA_node = a2 + N;
+  p.nA_score = (float*)(a2 + N + R);
+  p.nA_slot = a2 + N + 2 * R;
   p.B_cnt = (int32_t*)(ws + W.B_cnt);
   p.B_node = (int32_t*)(ws + W.B_node);
   p.B_slot = (int32_t*)(ws + W.B_slot);
@@ -2094,25 +1734,41 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
   p.node_parent = (int32_t*)(ws + W.node_parent);
   p.node_label = (int32_t*)(ws + W.node_label);
   p.child = (int32_t*)(ws + W.child);
+  p.st_h = (float*)(ws + W.st_h);
+  p.st_c = (float*)(ws + W.st_c);
+  p.pp = pp;
+  p.logp = logp;
+  p.G = (float*)(ws + W.v2_G);
+  p.E = (const float*)(ws + W.v2_E);
+  p.bias = (const float*)(ws + W.v2_bias);
+  p.plog = (const float*)(ws + W.v2_plog);
+  p.b_out = b_out;
+  p.hpl = (unsigned short*)(ws + W.v2_hpl);
+  p.hplane = (size_t)((R + 63) / 64 * 64) * H;
   p.N = N;
   p.w = w;
   p.V = V;
   p.bcap = W.bcap;
   p.maxn = W.maxn;
   p.R = R;
+  p.H = H;
+  p.L = L;
+  p.J = J;
+  p.NS = J / 32;
+  {
+    const char* e = getenv("MS_RNNT_PLANES");      // 3 = the exact three-bf16 operands (A/B runs); default: two fp16 planes
+    p.two = (e && e[0] == '3') ? 0 : 1;
+  }
   MS_HIP(hipMemsetAsync(p.child, 0xFF, (size_t)N * W.maxn * V * 4, s));
   hipLaunchKernelGGL(beam_init_kernel, dim3(ms::cdiv(N, 64)), dim3(64), 0, s, p);
   MS_LAUNCH_CHECK();
   {
-    const char* e = getenv("MS_RNNT_V2");
     // LDS of the re-cut sequence's two largest kernels, each against the 64 KB a launch gets without an attribute: the joint
     // (static red[8][32][33] + zs[64][33] = 42 240 B, dynamic W_out slice V1 x 32 floats) and the round kernel (candidates
     // w x V1 floats beside ~3 KB of static arrays).  Larger vocabularies take the round-4 sequence below.
     constexpr size_t JOINT_STATIC_LDS = (8 * 32 * 33 + 64 * 33) * sizeof(float);
-    if (!(e && e[0] == '0') && H % 64 == 0 && J % 32 == 0 && JOINT_STATIC_LDS + (size_t)V1 * 32 * 4 <= 64 * 1024 &&
-        (size_t)w * V1 * 4 <= 48 * 1024)
-      return beam2_decode(p, W, ws, embedding, w_ih, w_hh, b_ih, b_hh, w_pred, w_out, b_out, enc_p, out_idx, out_len, out_score, T,
-                          N, V, D, H, L, J, w, max_symbols, s);
+    if (H % 64 == 0 && J % 32 == 0 && JOINT_STATIC_LDS + (size_t)V1 * 32 * 4 <= 64 * 1024 && (size_t)w * V1 * 4 <= 48 * 1024)
+      return beam2_decode(p, net, W, ws, enc_p, out_idx, out_len, out_score, T, max_symbols, s);
   }
   int rc = predictor_step(net, W, ws, s);
   if (rc != MS_OK) return rc;
@@ -2131,8 +1787,7 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
         if (rc != MS_OK) return rc;
       }
     }
-    hipLaunchKernelGGL(beam_frame_end_kernel, dim3(w, N), dim3(256), 0, s, p, (float*)(ws + W.st_h), (float*)(ws + W.st_c), pp,
-                       t, L * H, J);
+    hipLaunchKernelGGL(beam_frame_end_kernel, dim3(w, N), dim3(256), 0, s, p, t);
     MS_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(beam_finish_kernel, dim3(N), dim3(64), 0, s, p, out_idx, out_len, out_score,

@@ -1466,18 +1466,26 @@ def test_rnnt_greedy_event_driven_decode_vs_oracle(ms, blank_bias, seed):
     assert dec(T(enc), T(lens)) == got                      # a second call re-uses the workspace
 
 
-@pytest.mark.parametrize("V,w,ms,N,steps,seed", [(4, 8, 3, 4, 24, 0), (11, 1, 2, 2, 12, 1), (6, 5, 4, 3, 10, 2),
-                                                 (28, 8, 3, 2, 8, 3), (3, 16, 2, 2, 16, 4),
-                                                 # vocabularies around the re-cut sequence's LDS gate (V + 1 <= 182): the last
-                                                 # one it serves, the first one that takes the round-4 sequence, and a BPE-sized one
-                                                 (181, 4, 2, 2, 8, 5), (182, 4, 2, 2, 8, 6), (255, 4, 2, 2, 6, 7)])
-def test_rnnt_device_decode_sweep(V, w, ms, N, steps, seed):
+@pytest.mark.parametrize("V,w,ms,N,steps,D,P,J,seed", [
+    # D = 8, P = 64, J = 32 (these cases keep the ids they had before D, P and J became parameters)
+    pytest.param(V, w, ms, N, steps, 8, 64, 32, seed, id=f"{V}-{w}-{ms}-{N}-{steps}-{seed}") for V, w, ms, N, steps, seed in [
+        (4, 8, 3, 4, 24, 0), (11, 1, 2, 2, 12, 1), (6, 5, 4, 3, 10, 2), (28, 8, 3, 2, 8, 3), (3, 16, 2, 2, 16, 4),
+        # vocabularies around the re-cut sequence's LDS gate (V + 1 <= 182): the last
+        # one it serves, the first one that takes the round-4 sequence, and a BPE-sized one
+        (181, 4, 2, 2, 8, 5), (182, 4, 2, 2, 8, 6), (255, 4, 2, 2, 6, 7)]] + [
+    # the remaining kernel forms at small sizes, each with non-empty oracle beam transcripts for at least three utterances (so
+    # that labels check the list code, not scores alone):
+    (4, 8, 3, 4, 24, 8, 128, 32, 10),     # re-cut sequence, one 32-row group per joint workgroup (H % 128 == 0)
+    (5, 8, 3, 5, 12, 64, 64, 48, 8),      # round-4 sequence (J % 32 != 0) on the fused predictor layer, 64-row form (R = 40);
+                                          # greedy on its 32-row form
+    (5, 8, 3, 5, 12, 64, 64, 32, 15)])    # re-cut sequence, two 32-row groups per joint workgroup; greedy on the fused predictor
+def test_rnnt_device_decode_sweep(V, w, ms, N, steps, D, P, J, seed):
     """Small vocabularies force same-prefix merges of blank transitions (the trie / logaddexp path); ragged lengths
     including an empty utterance; every width / round count against the oracle, greedy as well."""
     from myrtlespeech_amd.post_process.rnnt_decoder import RNNTBeamDecoder, RNNTGreedyDecoder
     from oracle import rnnt_oracle as RO
-    E, P = 24, 64
-    pred, joint, psd, jsd = _rnnt_parts(V=V, E=E, D=8, P=P, J=32, seed=seed)
+    E = 24
+    pred, joint, psd, jsd = _rnnt_parts(V=V, E=E, D=D, P=P, J=J, seed=seed)
     rng = np.random.default_rng(seed)
     enc = (rng.normal(size=(steps, N, E)) * 2.0).astype(np.float32)
     lens = np.sort(rng.integers(1, steps + 1, size=N))[::-1].copy()
