@@ -703,6 +703,39 @@ int ms_rnnt_loss_backward(const float* logits, const int32_t* in_lens, const int
                           const float* nll, const float* lattice, const float* grad_nll, float* grad, int N, int T, int U1,
                           int V1, int blank, void* stream);
 
+/* ---- RNN-T scoring without the logit lattice: the joint network fused into the loss's normaliser pass.  OWN specification;
+ *      restated in numpy by tests/rnnt_score_ref.py on top of tests/rnnt_loss_ref.py.
+ *
+ * nll[n] = -log P(y_n | audio_n) of ms_rnnt_loss_forward for the logits
+ *   x(n,t,u)[v] = sum_j w_out[v, j] tanh(enc_p[t N + n, j] + pred_p[u N + n, j]) + b_out[v]
+ * without ever storing them: for every EXISTING cell (t < T_n, u <= U_n) one MFMA kernel forms the row, its log-sum-exp Z
+ * (online over column tiles), and keeps b(t,u) = x[blank] - Z and e(t,u) = x[y_u] - Z (u < U_n) in the two skewed planes of
+ * the workspace; the loss's own lattice pass then gives alpha, beta and nll.  The recursion and EVERY edge case are those of
+ * ms_rnnt_loss_forward above: lengths out of range, a label out of range or equal to blank: nll = +inf; an impossible
+ * transcript (ll = -inf): +inf; a non-finite Z in an existing cell (a NaN anywhere in the cell's inputs, a +inf logit, a row
+ * of -inf only): NaN for that utterance alone.  A -inf in b_out is allowed and means "impossible symbol".  What lies in rows
+ * t >= T_n of enc_p, in rows u > U_n of pred_p and in targets past U_n changes no output bit.
+ *
+ * Inputs.  enc_p [T*N, J], row t N + n: the projected encoder frames, as ms_rnnt_decode takes them.  pred_p [U1*N, J], row
+ * u N + n: the projected predictor output after y_n[:u] (u = 0: after the start symbol).  w_out [V1, J], b_out [V1] or NULL
+ * (zeros).  in_lens, targets [N, U1 - 1] (NULL iff U1 == 1), tgt_lens, blank as for the loss.  J >= 1 and V1 >= 1 arbitrary.
+ * Arithmetic: the products are f16x3 (both operands split into fp16 hi + lo, three fp16 MFMAs, float32 accumulation),
+ * whatever MS_PRECISION says; error bound in tests/test_rnnt_score_gpu.py, stated for |w_out| within [2^-10, 2^10].
+ *
+ * Memory.  lattice is caller-owned float32 [2][N][T][U1] = alpha, beta (ms_rnnt_score_lattice_bytes = 8 N T U1; there is no
+ * Z plane: this call has no backward); only existing cells are defined.  ms_rnnt_score_workspace_bytes = the two skewed
+ * planes of the loss plus w_out split and packed in MFMA operand order (4 bytes per element of w_out padded to 128 symbols
+ * x 64 features); the workspace must be 16-byte aligned, is transient, and is rewritten by every call (the packing is one
+ * small launch of the call).  Both size queries are host arithmetic and return 0 for non-positive shapes.
+ * Supported: U1 <= 1024 (and N T U1 < 2^33 cells), as the loss; MS_ERR_UNSUPPORTED beyond, nothing launched.
+ * The call neither synchronises nor allocates.  Three launches (pack, cells, lattice); no workgroup waits on another, no
+ * atomics: the same inputs give the same bits. */
+size_t ms_rnnt_score_lattice_bytes(int N, int T, int U1);
+size_t ms_rnnt_score_workspace_bytes(int N, int T, int U1, int J, int V1);
+int ms_rnnt_score(const float* enc_p, const float* pred_p, const float* w_out, const float* b_out, const int32_t* in_lens,
+                  const int32_t* targets, const int32_t* tgt_lens, float* nll, float* lattice, int N, int T, int U1, int J,
+                  int V1, int blank, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@
 //                                         values of the row the recursion needs -- b = lp(blank), e = lp(y_u) -- into two
 //                                         transient planes of the workspace
 //   launch 2  rnnt_loss_lattice_kernel    2 N workgroups (alpha and beta of an utterance side by side), one thread per u,
-//                                         walking the anti-diagonals d = t + u
+//                                         walking the anti-diagonals d = t + u; launched through ms::rnnt_lattice_launch
+//                                         (rnnt_loss.h), which ms_rnnt_score (rnnt_score.hip) calls on planes of its own
 //   backward  rnnt_loss_grad_kernel       the row pass again: logits, Z, alpha, beta in, the grad row out; zeros for the cells
 //                                         that do not exist, in the same launch
 //
@@ -20,21 +21,20 @@
 #include <math.h>
 
 #include "common.h"
+#include "rnnt_loss.h"
 
 namespace {
 
-constexpr int RL_MAX_U1 = 1024;        // one thread per u: a workgroup
+// (shared with rnnt_score.hip: rnnt_loss.h)
+using ms::RL_MAX_U1;
+using ms::rl_label_ok;
+using ms::rl_lens_ok;
+using ms::rl_nan;
+using ms::rl_neg_inf;
+using ms::rl_skew_rows;
+using ms::rl_supported;
+
 constexpr int RL_ROW_THREADS = 256;
-
-__device__ __forceinline__ float rl_neg_inf() { return -INFINITY; }
-__device__ __forceinline__ float rl_nan() { return __uint_as_float(0x7fc00000u); }
-
-__host__ __device__ __forceinline__ size_t rl_skew_rows(int T, int U1) { return (size_t)T + U1 - 1; }
-
-// the caller's error otherwise: such an utterance has no cells, nll = +inf and a zero gradient
-__device__ __forceinline__ bool rl_lens_ok(int Tn, int Un, int T, int U1) { return Tn >= 1 && Tn <= T && Un >= 0 && Un <= U1 - 1; }
-
-__device__ __forceinline__ bool rl_label_ok(int lab, int V1, int blank) { return lab >= 0 && lab < V1 && lab != blank; }
 
 template <int G>
 __device__ __forceinline__ float rl_group_max(float v) {
@@ -318,14 +318,21 @@ inline int rl_group(int V1, bool vec) {
 
 inline bool rl_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// MS_ERR_UNSUPPORTED past the shapes the kernels serve (U1 <= 1024; a row-pass grid that fits 31 bits)
-inline bool rl_supported(int N, int T, int U1) {
-  if (U1 > RL_MAX_U1) return false;
-  const long R = (long)N * T * U1;
-  return (R + 3) / 4 <= 0x7fffffffL && (long)N * 2 <= 0x7fffffffL;
-}
-
 }  // namespace
+
+int ms::rnnt_lattice_launch(const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens, const float* b_sk,
+                            const float* e_sk, float* alpha, float* beta, float* nll, int N, int T, int U1, int V1, int blank,
+                            hipStream_t st) {
+  const int threads = ms::cdiv(U1, 64) * 64;
+  if (threads > 64)
+    hipLaunchKernelGGL(rnnt_loss_lattice_kernel<true>, dim3(2 * N), dim3(threads), 0, st, in_lens, targets, tgt_lens, b_sk, e_sk,
+                       alpha, beta, nll, T, U1, V1, blank);
+  else
+    hipLaunchKernelGGL(rnnt_loss_lattice_kernel<false>, dim3(2 * N), dim3(64), 0, st, in_lens, targets, tgt_lens, b_sk, e_sk,
+                       alpha, beta, nll, T, U1, V1, blank);
+  MS_LAUNCH_CHECK();
+  return MS_OK;
+}
 
 extern "C" size_t ms_rnnt_loss_lattice_bytes(int N, int T, int U1) {
   if (N <= 0 || T <= 0 || U1 <= 0) return 0;
@@ -365,15 +372,7 @@ extern "C" int ms_rnnt_loss_forward(const float* logits, const int32_t* in_lens,
   RL_ROW_LAUNCH(rnnt_loss_normalise_kernel, R, V1, vec, st, logits, in_lens, targets, tgt_lens, Z, b_sk, e_sk, R, T, U1, V1,
                 blank);
   MS_LAUNCH_CHECK();
-  const int threads = ms::cdiv(U1, 64) * 64;
-  if (threads > 64)
-    hipLaunchKernelGGL(rnnt_loss_lattice_kernel<true>, dim3(2 * N), dim3(threads), 0, st, in_lens, targets, tgt_lens, b_sk, e_sk,
-                       alpha, beta, nll, T, U1, V1, blank);
-  else
-    hipLaunchKernelGGL(rnnt_loss_lattice_kernel<false>, dim3(2 * N), dim3(64), 0, st, in_lens, targets, tgt_lens, b_sk, e_sk,
-                       alpha, beta, nll, T, U1, V1, blank);
-  MS_LAUNCH_CHECK();
-  return MS_OK;
+  return ms::rnnt_lattice_launch(in_lens, targets, tgt_lens, b_sk, e_sk, alpha, beta, nll, N, T, U1, V1, blank, st);
 }
 
 extern "C" int ms_rnnt_loss_backward(const float* logits, const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens,

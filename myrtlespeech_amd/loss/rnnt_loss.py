@@ -10,6 +10,10 @@ require grad the loss is an autograd node whose backward is ``ms_rnnt_loss_backw
 beta) the forward wrote, the module itself keeps no state and the workspace is transient.
 
 With ``RNNT.joint_lattice`` the ``none`` reduction scores a transcript under a model.
+
+``rnnt_score`` is the same -log P without the logits: it takes the joint network's two projected inputs and its output layer,
+and ``ms_rnnt_score`` forms each cell's row inside one MFMA kernel, keeping only the two numbers per cell the recursion needs
+(``RNNT.transcript_nll`` builds it from a model).  No gradient.
 """
 from typing import Tuple
 
@@ -132,3 +136,78 @@ class RNNTLoss(torch.nn.Module):
             return nll
         total = nll.sum()
         return total if self.reduction == "sum" else total / n
+
+
+def check_score_shapes(t, n, u1, j, v1, in_lens, targets, target_lens, blank):
+    """The validation of ``rnnt_score`` (that of ``RNNTLoss.forward``, for the fused scorer's arguments): ValueError before a
+    device is needed.  Returns the host int64 lengths."""
+    if min(t, n, u1, j, v1) <= 0:
+        raise ValueError(f"shapes T={t}, N={n}, U+1={u1}, J={j}, symbols={v1} have an empty dimension")
+    if u1 > MAX_U1:
+        raise ValueError(f"max_target_len + 1 = {u1} exceeds the supported {MAX_U1}")
+    if not 0 <= int(blank) < v1:
+        raise ValueError(f"blank={blank} must be in [0, {v1})")
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.shape[0] != n:
+        raise ValueError(f"targets must be [batch = {n}, max_target_len], got {tuple(getattr(targets, 'shape', ()))}")
+    if targets.shape[1] != u1 - 1:
+        raise ValueError(f"targets are padded to {targets.shape[1]} labels, pred_p holds {u1 - 1} + 1 rows")
+    if targets.is_floating_point():
+        raise ValueError("targets must be an integer tensor")
+    xl, yl = _int_lens(in_lens, "input lengths"), _int_lens(target_lens, "target lengths")
+    if xl.numel() != n or yl.numel() != n:
+        raise ValueError(f"lengths of batch {xl.numel()} / {yl.numel()} != batch {n}")
+    if int(xl.min()) < 1 or int(xl.max()) > t:
+        raise ValueError(f"input lengths must be in [1, {t}]")
+    if int(yl.min()) < 0 or int(yl.max()) > u1 - 1:
+        raise ValueError(f"target lengths must be in [0, {u1 - 1}]")
+    return xl, yl
+
+
+def rnnt_score(enc_p: torch.Tensor, pred_p: torch.Tensor, w_out: torch.Tensor, b_out, in_lens: torch.Tensor,
+               targets: torch.Tensor, target_lens: torch.Tensor, blank: int, return_lattice: bool = False):
+    """``nll[N] = -log P(y_n | audio_n)`` from the joint network's inputs -- ``ms_rnnt_score`` (include/ms_hotpath.h).
+
+    enc_p [T, N, J] projected encoder frames, pred_p [U + 1, N, J] projected predictor outputs (row u: after ``y_n[:u]``),
+    w_out [V + 1, J] and b_out [V + 1] (or None) the joint's output layer, targets [N, U] padded labels.  The logits
+    ``w_out . tanh(enc_p[t] + pred_p[u]) + b_out`` are never stored: memory is 8 bytes per cell plus the packed weights.
+    Returns nll, or ``(nll, lattice)`` with lattice [2, N, T, U + 1] = alpha, beta (defined on existing cells only).
+    Detached float32 device tensors; there is no backward."""
+    for name, x in (("enc_p", enc_p), ("pred_p", pred_p)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise ValueError(f"{name} must be [rows, batch, joint features]")
+    if not isinstance(w_out, torch.Tensor) or w_out.dim() != 2:
+        raise ValueError("w_out must be [symbols, joint features]")
+    t, n, j = enc_p.shape
+    u1 = pred_p.shape[0]
+    v1 = w_out.shape[0]
+    if pred_p.shape[1] != n or pred_p.shape[2] != j or w_out.shape[1] != j:
+        raise ValueError(f"enc_p {tuple(enc_p.shape)}, pred_p {tuple(pred_p.shape)} and w_out {tuple(w_out.shape)} do not agree "
+                         "in the batch or the joint features")
+    if b_out is not None and tuple(b_out.shape) != (v1,):
+        raise ValueError(f"b_out must be [{v1}], got {tuple(b_out.shape)}")
+    xl, yl = check_score_shapes(t, n, u1, j, v1, in_lens, targets, target_lens, blank)
+    _lib.require_gpu()
+    lib = _lib.load()
+    enc_p, pred_p, w = _lib.f32c(enc_p.detach()), _lib.f32c(pred_p.detach()), _lib.f32c(w_out.detach())
+    b = None if b_out is None else _lib.f32c(b_out.detach())
+    # ONE staged upload for what starts on the host (RNNTLoss.forward)
+    host_parts = [xl.to(torch.int32), yl.to(torch.int32)]
+    y_on_host = not targets.is_cuda
+    if y_on_host and targets.numel():
+        host_parts.append(targets.detach().to(torch.int32).reshape(-1))
+    packed = _lib.upload(torch.cat(host_parts))
+    xl_dev, yl_dev = packed[:n], packed[n:2 * n]
+    if not targets.numel():
+        y_dev = None                                       # U1 == 1: the ABI takes NULL
+    elif y_on_host:
+        y_dev = packed[2 * n:]
+    else:
+        y_dev = targets.detach().to(dtype=torch.int32).contiguous().reshape(-1)
+    nll = torch.empty(n, dtype=torch.float32, device="cuda")
+    lattice = torch.empty((2, n, t, u1), dtype=torch.float32, device="cuda")
+    nbytes = lib.ms_rnnt_score_workspace_bytes(n, t, u1, j, v1)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device="cuda")             # transient: nothing outlives the call
+    _lib.check(lib.ms_rnnt_score(_lib.ptr(enc_p), _lib.ptr(pred_p), _lib.ptr(w), _lib.ptr(b), _lib.ptr(xl_dev), _lib.ptr(y_dev),
+                                 _lib.ptr(yl_dev), _lib.ptr(nll), _lib.ptr(lattice), n, t, u1, j, v1, int(blank), _lib.ptr(ws),
+                                 ws.numel(), _lib.stream_ptr()), "ms_rnnt_score")
+    return (nll, lattice) if return_lattice else nll

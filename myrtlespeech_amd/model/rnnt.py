@@ -47,6 +47,28 @@ class RNNTPredictor(torch.nn.Module):
         (out, _), new_state = self.rnn((emb, torch.ones(r, dtype=torch.int64)), state)
         return out[0], new_state
 
+    def forward_targets(self, targets: torch.Tensor, target_lens: torch.Tensor) -> torch.Tensor:
+        """targets [N, U] padded labels -> pred [U + 1, N, hidden]: row u is the prediction after ``y_n[:u]`` (u = 0: after
+        the start symbol), for GIVEN transcripts.  ONE embedding look-up over ``[blank, y_0 .. y_{U-1}]`` of the whole batch
+        (time-major rows) and ONE call of the recurrent stack on the [U + 1, N, D] sequence from a zero state, where ``step``
+        (kept for the decoders) would take U + 1 rounds.  The predictor is causal, so what the padding of ``targets`` holds
+        (the look-up clamps it) only reaches rows u > target_lens[n]; ``target_lens`` is checked against the batch only."""
+        if targets.dim() != 2 or targets.is_floating_point():
+            raise ValueError(f"targets must be an integer tensor [N, U], got {tuple(targets.shape)} {targets.dtype}")
+        n, u_max = targets.shape
+        if n <= 0 or target_lens.numel() != n:
+            raise ValueError(f"target lengths of batch {target_lens.numel()} != targets batch {n}")
+        _lib.require_gpu()
+        w = _lib.f32c(self.embedding.weight.detach())
+        y = targets.detach().to(device="cuda", dtype=torch.int32)
+        idx = torch.cat([torch.full((1, n), self.blank, dtype=torch.int32, device="cuda"), y.t()], 0).contiguous()
+        rows = (u_max + 1) * n
+        emb = torch.empty((u_max + 1, n, w.shape[1]), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.load().ms_embedding_forward(_lib.ptr(w), _lib.ptr(idx), _lib.ptr(emb), rows, w.shape[1], w.shape[0],
+                                                    _lib.stream_ptr()), "ms_embedding_forward")
+        (out, _), _ = self.rnn((emb, torch.full((n,), u_max + 1, dtype=torch.int64)), self.zero_state(n))
+        return out
+
 
 class RNNTJoint(torch.nn.Module):
     def __init__(self, enc_features: int, pred_features: int, joint_features: int, vocab_size: int):
@@ -109,7 +131,9 @@ class RNNT(torch.nn.Module):
         Built from the decoders' pieces only (``predictor.step`` over blank and then the labels, ``joint.project_encoder``,
         ``joint.logprobs``) and detached: it serves scoring, not training.  The predictor is causal, so what the padding of
         ``targets`` holds (the embedding look-up clamps it) only reaches rows u > target_lens[n], which the loss never reads;
-        ``lens`` / ``target_lens`` are checked against the shapes and otherwise left to the loss."""
+        ``lens`` / ``target_lens`` are checked against the shapes and otherwise left to the loss.
+        This materialises N T (U + 1) (V + 1) floats in U + 1 rounds of small launches: for small alphabets and short
+        transcripts only.  ``transcript_nll`` gives the same -log P without the lattice."""
         _lib.require_gpu()
         if enc.dim() != 3 or targets.dim() != 2 or targets.shape[0] != enc.shape[1]:
             raise ValueError(f"enc must be [T, N, E] and targets [N, U], got {tuple(enc.shape)} and {tuple(targets.shape)}")
@@ -131,3 +155,26 @@ class RNNT(torch.nn.Module):
                 if u < u_max:
                     labels = y[:, u].contiguous()
         return out
+
+    def transcript_nll(self, enc: torch.Tensor, lens: torch.Tensor, targets: torch.Tensor, target_lens: torch.Tensor
+                       ) -> torch.Tensor:
+        """-log P(transcript | audio) per utterance, [N] float32 on the device, WITHOUT the logit lattice: enc [T, N, E]
+        encoder frames, targets [N, U] padded labels.  The same quantity as ``RNNTLoss(blank=V, reduction="none")`` on
+        ``joint_lattice`` (up to the bounds of tests/test_rnnt_score_gpu.py), from one projection of the encoder, one pass of
+        the predictor over the transcripts (``forward_targets``), one projection of its output and ``loss.rnnt_loss.rnnt_score``,
+        whose memory does not grow with the alphabet.  Detached: it serves scoring, not training."""
+        from myrtlespeech_amd.loss.rnnt_loss import check_score_shapes, rnnt_score
+        if enc.dim() != 3 or targets.dim() != 2 or targets.shape[0] != enc.shape[1]:
+            raise ValueError(f"enc must be [T, N, E] and targets [N, U], got {tuple(enc.shape)} and {tuple(targets.shape)}")
+        t, n, _ = enc.shape
+        u1 = targets.shape[1] + 1
+        w, b = self.joint.out.weight, self.joint.out.bias
+        blank = self.predictor.blank
+        check_score_shapes(t, n, u1, w.shape[1], w.shape[0], lens, targets, target_lens, blank)
+        _lib.require_gpu()
+        with torch.no_grad():
+            enc_p = self.joint.project_encoder(enc.detach())                    # [T*N, J], row t*N + n
+            pred = self.predictor.forward_targets(targets, target_lens)         # [U1, N, H]
+            pred_p = self.joint._linear(_lib.f32c(pred).reshape(u1 * n, -1), self.joint.pred_proj)   # [U1*N, J], row u*N + n
+            return rnnt_score(enc_p.reshape(t, n, -1), pred_p.reshape(u1, n, -1), w.detach(), None if b is None else b.detach(),
+                              lens, targets, target_lens, blank)
