@@ -124,6 +124,32 @@ int ms_maskconv_fwin_forward(const float* x, const int32_t* lens, const void* pa
                              int pad_f_l, int pad_t_l, int act, float act_lo, float act_hi, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* The pair single-channel convolution -> channels-last convolution without the float32 tensor between them:
+ * ms_maskconv_fwin_planes_forward is ms_maskconv_fwin_forward whose epilogue writes, instead of y, the hi / lo planes
+ * [N, Fout, Tout, Cout] that ms_maskconv_cl_forward's layout pass would make of y (same bias, clamp and split, so the
+ * same bits; Cout % 16 == 0) into `planes` (at least ms_maskconv_cl_workspace_bytes(N, Cout, Fout, Tout) bytes);
+ * ms_maskconv_cl_planes_forward is ms_maskconv_cl_forward on such planes, its layout pass skipped.  The first returns
+ * MS_ERR_UNSUPPORTED, with nothing launched, for shapes that only the kernels without a planes epilogue serve (short
+ * inputs, ms_conv_set_variant(1)): the caller then runs the two plain entry points.  The two *_supported queries say, without
+ * launching anything, whether the producer would write planes and whether the channels-last kernel takes the consumer's
+ * shape (it has no tile for e.g. 96 input channels at 11 taps: ms_maskconv_cl_forward then answers MS_ERR_UNSUPPORTED and
+ * its caller uses ms_maskconv_forward, which needs the float32 tensor): hand planes over only when both answer 1. */
+int ms_maskconv_fwin_planes_supported(int N, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST, int DT);
+int ms_maskconv_cl_supported(int N, int Cin, int Fin, int Cout, int Fout, int Tout, int KT, int ST, int DT);
+int ms_maskconv_fwin_planes_forward(const float* x, const int32_t* lens, const void* packed_w, const float* bias, void* planes,
+                                    size_t planes_bytes, int N, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT,
+                                    int SF, int ST, int DT, int pad_f_l, int pad_t_l, int act, float act_lo, float act_hi,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int ms_maskconv_cl_planes_forward(const int32_t* lens, const void* packed_w, const float* bias, float* y, int N, int Cin,
+                                  int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST, int DF,
+                                  int DT, int pad_f_l, int pad_t_l, int act, float act_lo, float act_hi, void* planes,
+                                  size_t planes_bytes, void* stream);
+
+/* Tuning switch for same-process A/B runs of the convolution front end: 0 = the shipped dispatch, 1 = every shape on the
+ * tiled kernel and layout passes that served it before the shared-window kernel (bit-identical results).  Not part of
+ * the reference surface. */
+int ms_conv_set_variant(int variant);
+
 /* MaskConv1d with many input channels as im2col + split-bf16 GEMM (model/cnn.py:295-333, the conv1d flavour of the DS2
  * builder): x [N, Cin, Tin] -> y [N, Cout, Tout]; frames t >= lens[n] read as zero (cnn.py:280-293), pad_l zero
  * frames on the left (cnn.py:252-278); packed = ms_maskconv1d_gemm_pack of weight [Cout, Cin, KT]; bias may be NULL;

@@ -39,7 +39,13 @@ struct ClP {
   // feature-window instantiation (single-channel input, ms_maskconv_fwin_*): the "channels" of output feature row fo are
   // the KF input feature rows of its window, read from planes [N][Tin][FP] at element offset fo * SF (KF = 1 in this struct)
   int FP;
+  // shared-window form of the feature-window kernel (maskconv_fwin_shared_kernel): a workgroup's output rows are CS apart, so
+  // that their windows start RG whole granules apart in one staged span of SG granules per frame; PQ = cdiv(PW, ST)
+  int CS, RG, SG, PQ;
 };
+
+// ms_conv_set_variant: 0 = the shipped dispatch, 1 = every shape on maskconv_cl_kernel and its layout passes
+std::atomic<int> g_conv_variant{0};
 
 __device__ __forceinline__ unsigned bf16b(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x); }
 __device__ __forceinline__ unsigned f16b(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x); }
@@ -358,6 +364,236 @@ int conv_cl_short_plan(const ClP& p, bool f16, int* RB, int* RIN, size_t* lds) {
   return 0;
 }
 
+// ---- long single-channel inputs (DS2 conv1 on whole utterances): the feature-window instantiation above stages a 48-row
+// window per output row -- neighbouring rows share 46 of its rows -- and all of a tile's filter taps, 138 KB of LDS: one
+// workgroup per CU and nothing under its staging loop.  Shared-window form: a workgroup owns output rows fo, fo + CS,
+// fo + 2 CS, ... (CS = 16 bytes over the byte distance of two neighbouring windows: 4 at feature stride 2), whose windows
+// start whole 16-byte granules apart, so ONE staged span per frame -- (rows - 1) RG + KG granules -- serves all of them with
+// aligned fragment reads: 24 B per frame, row and plane instead of 96.  Frames lie [granule][frame % ST][frame / ST], so the 32
+// lanes of a fragment read consecutive 16-byte slots.  The filters pass through LDS two taps at a time and the next stage's
+// granules are requested before the current stage's MFMAs: 78 KB per workgroup at the DS2 shape, two workgroups per CU.
+// 64 frames x 10 rows per workgroup; wave = (32-frame block, five rows), one A fragment feeds the five rows' MFMAs.
+// Per output element the MFMAs come in the order of maskconv_cl_kernel (kt, then s, then hi*hi, lo*hi, hi*lo): same bits.
+constexpr int FS_TT = 64;    // output frames per workgroup
+constexpr int FS_MR = 5;     // output rows per wave (two row groups per workgroup)
+constexpr int FS_TS = 2;     // taps per filter stage
+constexpr int FS_PF = 2;     // filter granules per thread, plane and stage
+
+template <int P>
+__global__ __launch_bounds__(256, 2) void maskconv_fwin_shared_kernel(const unsigned short* __restrict__ xh,
+                                                                      const unsigned short* __restrict__ xl,
+                                                                      const int32_t* __restrict__ lens,
+                                                                      const unsigned short* __restrict__ wp,
+                                                                      const float* __restrict__ bias, float* __restrict__ y,
+                                                                      unsigned short* __restrict__ oh,
+                                                                      unsigned short* __restrict__ ol, ClP p,
+                                                                      const float* __restrict__ scale_word) {
+  constexpr bool F16 = ms::prec_one_plane(P), HM = P == ms::PREC_F16X3;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  // input [plane][granule SG][frame % ST][PQ][16 B]  then one filter stage [plane][tap FS_TS][kg][32][16 B]
+  const int gran_bytes = p.ST * p.PQ * 16;
+  const int in_plane = p.SG * gran_bytes;
+  char* Ph = lds;
+  char* Pl = lds + in_plane;
+  char* Wh = lds + (F16 ? 1 : 2) * in_plane;
+  char* Wl = Wh + FS_TS * p.KG * 32 * 16;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, half = lane >> 5;
+  const int fb = wave & 1, rg = wave >> 1;    // this wave's frame block and row group
+  const int t0 = blockIdx.x * FS_TT;
+  const int cls = blockIdx.y % p.CS, jb = blockIdx.y / p.CS;
+  const int fo_first = cls + jb * (2 * FS_MR) * p.CS;
+  if (fo_first >= p.Fout) return;             // (whole workgroup)
+  const int nrows = min(2 * FS_MR, (p.Fout - 1 - fo_first) / p.CS + 1);
+  const int n = blockIdx.z / p.co_tiles, tile = blockIdx.z % p.co_tiles;
+  const int len = lens ? min(lens[n], p.Tin) : p.Tin;
+  const int cout_pad = p.co_tiles * 32;
+  const size_t wplane = (size_t)p.KT * p.KG * cout_pad * 8;  // elements
+
+  // the filter granules of a stage travel global -> registers -> LDS, so that the loads fly under the previous stage's MFMAs
+  u32x4 fh[FS_PF], fl[FS_PF];
+  auto load_filters = [&](int kt0) {
+    const int ng = min(FS_TS, p.KT - kt0) * p.KG * 32;
+#pragma unroll
+    for (int j = 0; j < FS_PF; ++j) {
+      const int i = tid + 256 * j;
+      if (i < ng) {
+        const int co = i & 31, rest = i >> 5;  // rest = kt_local*KG + kg
+        const size_t src = (((size_t)kt0 * p.KG + rest) * cout_pad + tile * 32 + co) * 8;
+        fh[j] = *reinterpret_cast<const u32x4*>(wp + src);
+        if (!F16) fl[j] = *reinterpret_cast<const u32x4*>(wp + wplane + src);
+      }
+    }
+  };
+  auto store_filters = [&](int kt0) {
+    const int ng = min(FS_TS, p.KT - kt0) * p.KG * 32;
+#pragma unroll
+    for (int j = 0; j < FS_PF; ++j) {
+      const int i = tid + 256 * j;
+      if (i < ng) {
+        *reinterpret_cast<u32x4*>(Wh + i * 16) = fh[j];
+        if (!F16) *reinterpret_cast<u32x4*>(Wl + i * 16) = fl[j];
+      }
+    }
+  };
+  load_filters(0);
+
+  // ---- stage the span of every frame once (masked, zero padded): 16 lanes = one frame's granules, contiguous in memory
+  {
+    const unsigned plane_bytes = (unsigned)((size_t)p.N * p.Tin * p.FP * 2);
+    const __amdgpu_buffer_rsrc_t xh_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(xh), 0, plane_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xl_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(xl), 0, plane_bytes, 0x00020000);
+    const int tin0 = t0 * p.ST - p.pad_t;
+    const int g = tid & 15;
+    const int span = (nrows - 1) * p.RG + p.KG;     // granules the valid rows read: inside the frame's FP elements
+    if (g < span) {
+      for (int q = tid >> 4; q < p.PW; q += 16) {
+        const int tin = tin0 + q;
+        u32x4 vh = {0u, 0u, 0u, 0u}, vl = {0u, 0u, 0u, 0u};
+        if (tin >= 0 && tin < len) {
+          // (element offset fo_first * SF is even: 4-byte aligned 16-byte buffer loads, as in maskconv_cl_kernel)
+          const int boff = (int)((((size_t)n * p.Tin + tin) * p.FP + (size_t)fo_first * p.SF + g * 8) * 2);
+          vh = __builtin_amdgcn_raw_buffer_load_b128(xh_rsrc, boff, 0, 0);
+          if (!F16) vl = __builtin_amdgcn_raw_buffer_load_b128(xl_rsrc, boff, 0, 0);
+        }
+        const int qq = q / p.ST, qr = q - qq * p.ST;
+        const int off = g * gran_bytes + (qr * p.PQ + qq) * 16;
+        *reinterpret_cast<u32x4*>(Ph + off) = vh;
+        if (!F16) *reinterpret_cast<u32x4*>(Pl + off) = vl;
+      }
+    }
+  }
+  store_filters(0);
+  __syncthreads();
+
+  ms::f32x16 acc[FS_MR];
+#pragma unroll
+  for (int f = 0; f < FS_MR; ++f)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[f][r] = 0.f;
+
+  // rows past the block's last one compute its last row again (no branch in the MFMA loop) and are not stored
+  int row_off[FS_MR];
+#pragma unroll
+  for (int f = 0; f < FS_MR; ++f) row_off[f] = min(rg * FS_MR + f, nrows - 1) * p.RG * gran_bytes;
+
+  for (int kt0 = 0; kt0 < p.KT; kt0 += FS_TS) {
+    const int ntap = min(FS_TS, p.KT - kt0);
+    const bool more = kt0 + FS_TS < p.KT;
+    if (more) load_filters(kt0 + FS_TS);
+    for (int ktl = 0; ktl < ntap; ++ktl) {
+      // frame (fb*32 + l31)*ST + kt*DT sits in slot [kt*DT % ST][fb*32 + l31 + kt*DT / ST]
+      const int kd = (kt0 + ktl) * p.DT, kq = kd / p.ST, kr = kd - kq * p.ST;
+      const int lane_off = (kr * p.PQ + kq + fb * 32 + l31) * 16;
+      for (int s = 0; s < p.KG / 2; ++s) {
+        const int kg = 2 * s + half;
+        const int woff = ((ktl * p.KG + kg) * 32 + l31) * 16;
+        const u32x4 ah = *reinterpret_cast<const u32x4*>(Wh + woff);
+        u32x4 al = ah;
+        if (!F16) al = *reinterpret_cast<const u32x4*>(Wl + woff);
+#pragma unroll
+        for (int f = 0; f < FS_MR; ++f) {
+          const int poff = row_off[f] + kg * gran_bytes + lane_off;
+          const u32x4 bh = *reinterpret_cast<const u32x4*>(Ph + poff);
+          if (F16) {
+            acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh), acc[f], 0, 0, 0);
+          } else {
+            const u32x4 bl = *reinterpret_cast<const u32x4*>(Pl + poff);
+            acc[f] = ms::mfma_32x32x16<HM>(ah, bh, acc[f]);
+            acc[f] = ms::mfma_32x32x16<HM>(al, bh, acc[f]);
+            acc[f] = ms::mfma_32x32x16<HM>(ah, bl, acc[f]);
+          }
+        }
+      }
+    }
+    if (more) {
+      __syncthreads();   // this stage's filter reads are done
+      store_filters(kt0 + FS_TS);
+      __syncthreads();
+    }
+  }
+
+  const int t = t0 + fb * 32 + l31;
+  const float winv = scale_word[1];
+  if (t < p.Tout) {
+#pragma unroll
+    for (int f = 0; f < FS_MR; ++f) {
+      const int j = rg * FS_MR + f;
+      if (j >= nrows) continue;
+      const int fo = fo_first + j * p.CS;
+      if (oh) {
+        // the next convolution's channels-last planes [N][Fout][Tout][Cout] (nchw_to_cl_split_kernel's layout and split, on
+        // the same clamped value): a lane holds 4 consecutive channels per register group, 8 bytes per plane
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const int co = tile * 32 + ms::mfma32_row(4 * r4, lane);
+          if (co >= p.Cout) continue;           // (Cout % 4 == 0: the group is whole)
+          unsigned h[4], l[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float v = acc[f][4 * r4 + e] * winv + (bias ? bias[co + e] : 0.f);
+            if (p.act == MS_ACT_CLAMP) v = fminf(fmaxf(v, p.lo), p.hi);
+            split_by_prec(v, P, h[e], l[e]);
+          }
+          const size_t o = (((size_t)n * p.Fout + fo) * p.Tout + t) * p.Cout + co;
+          *reinterpret_cast<u32x2*>(oh + o) = u32x2{h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
+          if (!F16) *reinterpret_cast<u32x2*>(ol + o) = u32x2{l[0] | (l[1] << 16), l[2] | (l[3] << 16)};
+        }
+        continue;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int co = tile * 32 + ms::mfma32_row(r, lane);
+        if (co < p.Cout) {
+          float v = acc[f][r] * winv + (bias ? bias[co] : 0.f);   // (winv: the packed weights' 2^-s, exact)
+          if (p.act == MS_ACT_CLAMP) v = fminf(fmaxf(v, p.lo), p.hi);
+          y[(((size_t)n * p.Cout + co) * p.Fout + fo) * p.Tout + t] = v;
+        }
+      }
+    }
+  }
+}
+
+// Does the shared-window form serve this feature-window problem (p as ms_maskconv_fwin_forward fills it)?  Fills CS, RG, SG,
+// PW, PQ and *lds.
+int conv_fs_plan(ClP& p, bool f16, size_t* lds) {
+  if (g_conv_variant.load(std::memory_order_relaxed) != 0 || p.Tout <= 48 || p.SF % 2) return 0;
+  int g = 2 * p.SF, b = 16;
+  while (b) { const int r = g % b; g = b; b = r; }        // gcd(16, bytes between neighbouring windows)
+  p.CS = 16 / g;
+  p.RG = p.CS * p.SF / 8;
+  p.SG = (2 * FS_MR - 1) * p.RG + p.KG;
+  p.PW = (FS_TT - 1) * p.ST + (p.KT - 1) * p.DT + 1;
+  p.PQ = ms::cdiv(p.PW, p.ST);
+  const int planes = f16 ? 1 : 2;
+  *lds = (size_t)planes * ((size_t)p.SG * p.ST * p.PQ * 16 + (size_t)FS_TS * p.KG * 32 * 16);
+  const long rows_y = (long)p.CS * ms::cdiv(ms::cdiv(p.Fout, p.CS), 2 * FS_MR);
+  if (p.SG > 16 || FS_TS * p.KG * 32 > 256 * FS_PF || *lds > 160 * 1024 || rows_y > 65535 || (long)p.N * p.co_tiles > 65535)
+    return 0;
+  return 1;
+}
+
+int conv_fs_launch(const ClP& p, size_t lds, const unsigned short* xh, const unsigned short* xl, const int32_t* lens,
+                   const void* packed_w, const float* bias, float* y, unsigned short* oh, unsigned short* ol,
+                   hipStream_t stream, const float* scale_word) {
+  static ms::DeviceOnce attr_once;
+  if (attr_once.need()) {
+    MS_HIP(hipFuncSetAttribute((const void*)maskconv_fwin_shared_kernel<ms::PREC_BF16X3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MS_HIP(hipFuncSetAttribute((const void*)maskconv_fwin_shared_kernel<ms::PREC_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MS_HIP(hipFuncSetAttribute((const void*)maskconv_fwin_shared_kernel<ms::PREC_F16X3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_once.done();
+  }
+  const int prec = ms::split_mode();
+  const dim3 grid(ms::cdiv(p.Tout, FS_TT), p.CS * ms::cdiv(ms::cdiv(p.Fout, p.CS), 2 * FS_MR), p.N * p.co_tiles);
+  const unsigned short* wq = (const unsigned short*)packed_w;
+  auto kern = prec == ms::PREC_F16 ? maskconv_fwin_shared_kernel<ms::PREC_F16>
+              : prec == ms::PREC_F16X3 ? maskconv_fwin_shared_kernel<ms::PREC_F16X3> : maskconv_fwin_shared_kernel<ms::PREC_BF16X3>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, xh, xl, lens, wq, bias, y, oh, ol, p, scale_word);
+  MS_LAUNCH_CHECK();
+  return MS_OK;
+}
+
 // f32 NCHW [N][C][F][T] -> channels-last bf16 hi / lo planes [N][F][T][C]  (C % 8 == 0)
 __global__ void nchw_to_cl_split_kernel(const float* __restrict__ x, unsigned short* __restrict__ hi,
                                         unsigned short* __restrict__ lo, int C, int F, int T, int prec) {
@@ -505,12 +741,31 @@ extern "C" size_t ms_maskconv_fwin_workspace_bytes(int N, int Tin, int KF, int S
   return ms::align_up((size_t)N * Tin * fwin_fp(KF, SF, Fout) * 4, 256);  // hi + lo planes
 }
 
-extern "C" int ms_maskconv_fwin_forward(const float* x, const int32_t* lens, const void* packed_w, const float* bias, float* y,
-                                        int N, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST,
-                                        int DT, int pad_f_l, int pad_t_l, int act, float act_lo, float act_hi, void* workspace,
-                                        size_t workspace_bytes, void* stream_) {
+// The feature-window problem of a single-channel convolution as the kernels see it (ms_maskconv_fwin_forward's arguments)
+static ClP fwin_params(int N, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST, int DT, int pad_t_l) {
+  ClP p{};
+  p.N = N; p.Cin = fwin_kfp(KF); p.Fin = 1; p.Tin = Tin; p.Cout = Cout; p.Fout = Fout; p.Tout = Tout; p.KF = 1; p.KT = KT;
+  p.SF = SF; p.ST = ST; p.DF = 1; p.DT = DT; p.pad_f = 0; p.pad_t = pad_t_l; p.KG = p.Cin / 8;
+  p.co_tiles = ms::cdiv(Cout, 32);
+  p.FP = fwin_fp(KF, SF, Fout);
+  return p;
+}
+
+// Which kernel serves it: -1 = maskconv_fwin_shared_kernel, 4 / 1 = that tile of maskconv_cl_kernel, 0 = none.  Fills p's
+// staging fields and *lds for the kernel chosen.
+static int fwin_route(ClP& p, size_t* lds) {
+  if ((size_t)p.N * p.Tin * p.FP * 2 >= ((size_t)1 << 31)) return 0;      // the window loads' byte offsets are ints
+  if (conv_fs_plan(p, ms::split_mode() == ms::PREC_F16, lds)) return -1;
+  return conv_cl_plan(p, lds);
+}
+
+// y, or (planes != nullptr) the channels-last hi / lo planes of the output for ms_maskconv_cl_planes_forward
+static int fwin_forward(const float* x, const int32_t* lens, const void* packed_w, const float* bias, float* y, void* planes,
+                        int N, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST, int DT,
+                        int pad_f_l, int pad_t_l, int act, float act_lo, float act_hi, void* workspace,
+                        size_t workspace_bytes, void* stream_) {
   ms::ProfScope prof_span(MS_PROF_CONV, (hipStream_t)stream_);
-  MS_REQUIRE(x && packed_w && y && workspace, "null pointer");
+  MS_REQUIRE(x && packed_w && (y || planes) && workspace, "null pointer");
   MS_REQUIRE(N > 0 && Fin > 0 && Tin > 0 && Cout > 0 && Fout > 0 && Tout > 0, "bad shape");
   MS_REQUIRE(KF > 0 && KT > 0 && SF > 0 && ST > 0 && DT > 0 && pad_f_l >= 0 && pad_t_l >= 0, "bad kernel");
   MS_REQUIRE(SF % 2 == 0, "feature stride must be even (4-byte aligned window loads)");
@@ -520,27 +775,67 @@ extern "C" int ms_maskconv_fwin_forward(const float* x, const int32_t* lens, con
     return MS_ERR_WORKSPACE;
   }
   hipStream_t stream = (hipStream_t)stream_;
-  ClP p;
-  p.N = N; p.Cin = fwin_kfp(KF); p.Fin = 1; p.Tin = Tin; p.Cout = Cout; p.Fout = Fout; p.Tout = Tout; p.KF = 1; p.KT = KT;
-  p.SF = SF; p.ST = ST; p.DF = 1; p.DT = DT; p.pad_f = 0; p.pad_t = pad_t_l; p.KG = p.Cin / 8;
-  p.co_tiles = ms::cdiv(Cout, 32);
+  ClP p = fwin_params(N, Tin, Cout, Fout, Tout, KF, KT, SF, ST, DT, pad_t_l);
   p.act = act; p.lo = act_lo; p.hi = act_hi;
-  p.FP = fwin_fp(KF, SF, Fout);
   size_t lds = 0;
-  const int wf = conv_cl_plan(p, &lds);
-  if (wf == 0 || (size_t)N * Tin * p.FP * 2 >= ((size_t)1 << 31)) {
-    ms::set_error("ms_maskconv_fwin_forward: shape outside the LDS / grid budget");
+  const int route = fwin_route(p, &lds);
+  if (route == 0 || (planes && route != -1)) {
+    ms::set_error(planes ? "ms_maskconv_fwin_planes_forward: shape not served by the shared-window kernel"
+                         : "ms_maskconv_fwin_forward: shape outside the LDS / grid budget");
     return MS_ERR_UNSUPPORTED;
   }
   unsigned short* xh = (unsigned short*)workspace;
   unsigned short* xl = xh + (size_t)N * Tin * p.FP;
-  const int prec = ms::split_mode();
-  const bool f16 = prec == ms::PREC_F16;
   hipLaunchKernelGGL(ft_to_tf_split_kernel, dim3(ms::cdiv(Tin, 32), ms::cdiv(p.FP, 32), N), dim3(32, 8), 0, stream, x, xh, xl,
-                     Fin, Tin, p.FP, pad_f_l, prec);
+                     Fin, Tin, p.FP, pad_f_l, ms::split_mode());
   MS_LAUNCH_CHECK();
-  return conv_cl_launch<true>(p, wf, lds, xh, xl, lens, packed_w, bias, y, stream,
-                              (const float*)((const char*)packed_w + fwin_plane_bytes(Cout, KF, KT)));
+  const float* scale_word = (const float*)((const char*)packed_w + fwin_plane_bytes(Cout, KF, KT));
+  if (route == -1) {
+    unsigned short* oh = (unsigned short*)planes;
+    unsigned short* ol = oh ? oh + (size_t)N * Cout * Fout * Tout : nullptr;
+    return conv_fs_launch(p, lds, xh, xl, lens, packed_w, bias, y, oh, ol, stream, scale_word);
+  }
+  return conv_cl_launch<true>(p, route, lds, xh, xl, lens, packed_w, bias, y, stream, scale_word);
+}
+
+// Would ms_maskconv_fwin_planes_forward run this shape (1) or answer MS_ERR_UNSUPPORTED (0)?  Launches nothing.
+extern "C" int ms_maskconv_fwin_planes_supported(int N, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST,
+                                                 int DT) {
+  if (N <= 0 || Tin <= 0 || Cout <= 0 || Cout % 16 || Fout <= 0 || Tout <= 0 || KF <= 0 || KT <= 0 || SF <= 0 || SF % 2 ||
+      ST <= 0 || DT <= 0)
+    return 0;
+  ClP p = fwin_params(N, Tin, Cout, Fout, Tout, KF, KT, SF, ST, DT, 0);
+  size_t lds = 0;
+  return fwin_route(p, &lds) == -1;
+}
+
+extern "C" int ms_maskconv_fwin_forward(const float* x, const int32_t* lens, const void* packed_w, const float* bias, float* y,
+                                        int N, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST,
+                                        int DT, int pad_f_l, int pad_t_l, int act, float act_lo, float act_hi, void* workspace,
+                                        size_t workspace_bytes, void* stream_) {
+  MS_REQUIRE(y, "null pointer");
+  return fwin_forward(x, lens, packed_w, bias, y, nullptr, N, Fin, Tin, Cout, Fout, Tout, KF, KT, SF, ST, DT, pad_f_l, pad_t_l,
+                      act, act_lo, act_hi, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int ms_maskconv_fwin_planes_forward(const float* x, const int32_t* lens, const void* packed_w, const float* bias,
+                                               void* planes, size_t planes_bytes, int N, int Fin, int Tin, int Cout, int Fout,
+                                               int Tout, int KF, int KT, int SF, int ST, int DT, int pad_f_l, int pad_t_l,
+                                               int act, float act_lo, float act_hi, void* workspace, size_t workspace_bytes,
+                                               void* stream_) {
+  MS_REQUIRE(planes, "null pointer");
+  MS_REQUIRE(Cout > 0 && Cout % 16 == 0, "planes out need Cout % 16 == 0 (the next convolution's k-steps)");
+  if (N <= 0 || Fout <= 0 || Tout <= 0 || planes_bytes < ms_maskconv_cl_workspace_bytes(N, Cout, Fout, Tout)) {
+    ms::set_error("ms_maskconv_fwin_planes_forward: planes buffer too small");
+    return MS_ERR_WORKSPACE;
+  }
+  return fwin_forward(x, lens, packed_w, bias, nullptr, planes, N, Fin, Tin, Cout, Fout, Tout, KF, KT, SF, ST, DT, pad_f_l,
+                      pad_t_l, act, act_lo, act_hi, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int ms_conv_set_variant(int v) {
+  g_conv_variant.store(v, std::memory_order_relaxed);
+  return MS_OK;
 }
 
 static size_t cl_plane_bytes(int Cout, int Cin, int KF, int KT) {
@@ -571,12 +866,26 @@ extern "C" size_t ms_maskconv_cl_workspace_bytes(int N, int Cin, int Fin, int Ti
   return ms::align_up((size_t)N * Cin * Fin * Tin * 4, 256);  // hi + lo planes of the input
 }
 
-extern "C" int ms_maskconv_cl_forward(const float* x, const int32_t* lens, const void* packed_w, const float* bias, float* y,
-                                      int N, int Cin, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT,
-                                      int SF, int ST, int DF, int DT, int pad_f_l, int pad_t_l, int act, float act_lo,
-                                      float act_hi, void* workspace, size_t workspace_bytes, void* stream_) {
+// Would ms_maskconv_cl_forward / ms_maskconv_cl_planes_forward run this shape (1) or answer MS_ERR_UNSUPPORTED or a grid
+// limit (0)?  Launches nothing: a caller that hands planes over asks BEFORE the producer runs, since after it there is no
+// float32 tensor left for another kernel.
+extern "C" int ms_maskconv_cl_supported(int N, int Cin, int Fin, int Cout, int Fout, int Tout, int KT, int ST, int DT) {
+  if (N <= 0 || Cin <= 0 || Cin % 16 || Fin <= 0 || Cout <= 0 || Fout <= 0 || Tout <= 0 || KT <= 0 || ST <= 0 || DT <= 0 ||
+      (long)N * Fin > 65535)
+    return 0;
+  ClP p{};
+  p.N = N; p.Fout = Fout; p.Tout = Tout; p.KT = KT; p.ST = ST; p.DT = DT; p.KG = Cin / 8; p.co_tiles = ms::cdiv(Cout, 32);
+  size_t lds = 0;
+  return conv_cl_plan(p, &lds) != 0;
+}
+
+// x == nullptr: the workspace already holds the input's planes (ms_maskconv_fwin_planes_forward wrote them)
+static int cl_forward(const float* x, const int32_t* lens, const void* packed_w, const float* bias, float* y,
+                      int N, int Cin, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT,
+                      int SF, int ST, int DF, int DT, int pad_f_l, int pad_t_l, int act, float act_lo,
+                      float act_hi, void* workspace, size_t workspace_bytes, void* stream_) {
   ms::ProfScope prof_span(MS_PROF_CONV, (hipStream_t)stream_);
-  MS_REQUIRE(x && packed_w && y && workspace, "null pointer");
+  MS_REQUIRE(packed_w && y && workspace, "null pointer");
   MS_REQUIRE(N > 0 && Cin > 0 && Cin % 16 == 0 && Fin > 0 && Tin > 0 && Cout > 0 && Fout > 0 && Tout > 0, "bad shape");
   MS_REQUIRE(KF > 0 && KT > 0 && SF > 0 && ST > 0 && DF > 0 && DT > 0 && pad_f_l >= 0 && pad_t_l >= 0, "bad kernel");
   MS_REQUIRE(act == MS_ACT_NONE || act == MS_ACT_CLAMP, "bad act");
@@ -591,6 +900,7 @@ extern "C" int ms_maskconv_cl_forward(const float* x, const int32_t* lens, const
   p.co_tiles = ms::cdiv(Cout, 32);
   p.act = act; p.lo = act_lo; p.hi = act_hi;
   p.FP = 0;
+  p.CS = p.RG = p.SG = p.PQ = 0;
   size_t lds = 0;
   const int wf = conv_cl_plan(p, &lds);
   if (wf == 0) {
@@ -603,9 +913,11 @@ extern "C" int ms_maskconv_cl_forward(const float* x, const int32_t* lens, const
   MS_REQUIRE(N * Fin <= 65535, "N*Fin exceeds grid limits");
   const int prec = ms::split_mode();
   const bool f16 = prec == ms::PREC_F16;
-  hipLaunchKernelGGL(nchw_to_cl_split_kernel, dim3(ms::cdiv(Tin, 32), ms::cdiv(Cin, 32), N * Fin), dim3(32, 8), 0, stream, x,
-                     xh, xl, Cin, Fin, Tin, prec);
-  MS_LAUNCH_CHECK();
+  if (x) {
+    hipLaunchKernelGGL(nchw_to_cl_split_kernel, dim3(ms::cdiv(Tin, 32), ms::cdiv(Cin, 32), N * Fin), dim3(32, 8), 0, stream, x,
+                       xh, xl, Cin, Fin, Tin, prec);
+    MS_LAUNCH_CHECK();
+  }
   {
     int RB = 0, RIN = 0;
     size_t slds = 0;
@@ -629,4 +941,21 @@ extern "C" int ms_maskconv_cl_forward(const float* x, const int32_t* lens, const
     }
   }
   return conv_cl_launch<false>(p, wf, lds, xh, xl, lens, packed_w, bias, y, stream, scale_word);
+}
+
+extern "C" int ms_maskconv_cl_forward(const float* x, const int32_t* lens, const void* packed_w, const float* bias, float* y,
+                                      int N, int Cin, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT,
+                                      int SF, int ST, int DF, int DT, int pad_f_l, int pad_t_l, int act, float act_lo,
+                                      float act_hi, void* workspace, size_t workspace_bytes, void* stream_) {
+  MS_REQUIRE(x, "null pointer");
+  return cl_forward(x, lens, packed_w, bias, y, N, Cin, Fin, Tin, Cout, Fout, Tout, KF, KT, SF, ST, DF, DT, pad_f_l, pad_t_l,
+                    act, act_lo, act_hi, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int ms_maskconv_cl_planes_forward(const int32_t* lens, const void* packed_w, const float* bias, float* y, int N,
+                                             int Cin, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF,
+                                             int ST, int DF, int DT, int pad_f_l, int pad_t_l, int act, float act_lo,
+                                             float act_hi, void* planes, size_t planes_bytes, void* stream_) {
+  return cl_forward(nullptr, lens, packed_w, bias, y, N, Cin, Fin, Tin, Cout, Fout, Tout, KF, KT, SF, ST, DF, DT, pad_f_l,
+                    pad_t_l, act, act_lo, act_hi, planes, planes_bytes, stream_);
 }

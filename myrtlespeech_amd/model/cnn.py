@@ -109,6 +109,21 @@ class _PackedFilters:
         return self.buf
 
 
+def _geometry(x_shape, weight4: torch.Tensor, stride, dilation, same: bool, time_pads: Optional[Tuple[int, int]] = None):
+    """(pad_f, pad_t, fout, tout) of a convolution over an input of shape ``x_shape``: (left, right) zero padding per axis
+    and the output's feature and frame counts."""
+    _, _, fin, tin = x_shape
+    _, _, kf, kt = weight4.shape
+    (sf, st), (df, dt) = stride, dilation
+    pt = pad_same(tin, kt, st, dt) if same else (0, 0)
+    pf = pad_same(fin, kf, sf, df) if same else (0, 0)
+    if time_pads is not None:
+        pt = (int(time_pads[0]), int(time_pads[1]))
+    fout = (fin + sum(pf) - (df * (kf - 1) + 1)) // sf + 1
+    tout = (tin + sum(pt) - (dt * (kt - 1) + 1)) // st + 1
+    return pf, pt, fout, tout
+
+
 def _conv_forward(x4: torch.Tensor, seq_lens: torch.Tensor, weight4: torch.Tensor, bias: Optional[torch.Tensor],
                   packed: _PackedFilters, stride, dilation, groups: int, same: bool,
                   act: Optional[Tuple[float, float]], time_pads: Optional[Tuple[int, int]] = None):
@@ -118,15 +133,7 @@ def _conv_forward(x4: torch.Tensor, seq_lens: torch.Tensor, weight4: torch.Tenso
     n, cin, fin, tin = x4.shape
     cout, _, kf, kt = weight4.shape
     (sf, st), (df, dt) = stride, dilation
-    if same:
-        pt = pad_same(tin, kt, st, dt)
-        pf = pad_same(fin, kf, sf, df)
-    else:
-        pt = pf = (0, 0)
-    if time_pads is not None:
-        pt = (int(time_pads[0]), int(time_pads[1]))
-    fout = (fin + sum(pf) - (df * (kf - 1) + 1)) // sf + 1
-    tout = (tin + sum(pt) - (dt * (kt - 1) + 1)) // st + 1
+    pf, pt, fout, tout = _geometry(x4.shape, weight4, stride, dilation, same, time_pads)
     if fout <= 0 or tout <= 0:
         raise RuntimeError("convolution output would be empty")
     # lengths arithmetic on the host values (same float32 formula, same dtype as the input), uploaded without blocking
@@ -180,6 +187,82 @@ def _conv_forward(x4: torch.Tensor, seq_lens: torch.Tensor, weight4: torch.Tenso
                                        fin, tin, cout, fout, tout, kf, kt, sf, st, df, dt, pf[0], pt[0], groups, a, lo,
                                        hi, _lib.stream_ptr()), "ms_maskconv_forward")
     return y, new_lens
+
+
+def _has_forward_hooks(m: torch.nn.Module) -> bool:
+    """Would ``m(...)`` run anything besides ``m.forward`` (hooks on the module, or registered for every module)?"""
+    mod = torch.nn.modules.module
+    return bool(m._forward_hooks or m._forward_pre_hooks or mod._global_forward_hooks or mod._global_forward_pre_hooks)
+
+
+def conv_pair_forward(m1: "MaskConv2d", act1: Tuple[float, float], m2: "MaskConv2d", act2: Optional[Tuple[float, float]], x):
+    """``m2(m1(x), clamp act1 between, clamp act2 after)`` for a single-channel ``m1`` on the feature-window kernel followed by
+    an ``m2`` on the channels-last kernel (DS2's two convolutions), without the float32 tensor between them: ``m1``'s epilogue
+    writes the hi / lo planes that ``m2``'s layout pass would make of it straight into ``m2``'s workspace (conv_cl.hip,
+    ms_maskconv_fwin_planes_forward / ms_maskconv_cl_planes_forward) -- the same bits as the two calls.  Returns None, with
+    nothing launched, when either convolution would take another route in ``_conv_forward`` or carries a forward hook; the
+    caller then makes the two calls.  (The reference masks the intermediate tensor in place past each length; without a hook on
+    ``m1`` nobody can hold that tensor here, and ``m2``'s load predicates ignore what lies past a length.)"""
+    acts, seq_lens = x
+    if not (_lib.split_precision() and acts.is_cuda and acts.dtype == torch.float32 and acts.dim() == 4):
+        return None
+    if m1.groups != 1 or m2.groups != 1 or os.environ.get("MS_CONV_FWIN") == "0":
+        return None
+    if _has_forward_hooks(m1) or _has_forward_hooks(m2):
+        return None      # a hook sees a module's call and its output (m1's: the intermediate tensor): make the two calls
+    w1, w2 = m1.weight, m2.weight
+    n, cin1, fin1, tin1 = acts.shape
+    cout1, _, kf1, kt1 = w1.shape
+    cout2, cin2, kf2, kt2 = w2.shape
+    (sf1, st1), (df1, dt1) = _pair(m1.stride), _pair(m1.dilation)
+    (sf2, st2), (df2, dt2) = _pair(m2.stride), _pair(m2.dilation)
+    same1, same2 = m1._padding_mode == PaddingMode.SAME, m2._padding_mode == PaddingMode.SAME
+    pf1, pt1, fout1, tout1 = _geometry(acts.shape, w1, (sf1, st1), (df1, dt1), same1)
+    if fout1 <= 0 or tout1 <= 0 or cin1 != 1 or w1.shape[1] != 1 or cin2 != cout1:
+        return None
+    pf2, pt2, fout2, tout2 = _geometry((n, cout1, fout1, tout1), w2, (sf2, st2), (df2, dt2), same2)
+    if fout2 <= 0 or tout2 <= 0:
+        return None
+    # the routes of _conv_forward: m1 on the feature-window kernel, m2 on the channels-last one
+    flops1 = 2.0 * n * cout1 * fout1 * tout1 * kf1 * kt1
+    flops2 = 2.0 * n * cout2 * fout2 * tout2 * cin2 * kf2 * kt2
+    if not (df1 == 1 and sf1 % 2 == 0 and kf1 >= 16 and flops1 >= float(os.environ.get("MS_CONV_MFMA_MIN_FLOPS", "2e8"))):
+        return None
+    if not (cin2 % 16 == 0 and flops2 >= float(os.environ.get("MS_CONV_MFMA_MIN_FLOPS", "1e9"))):
+        return None
+    if fout1 == 1 and kf2 == 1 and sf2 == 1 and pf2 == (0, 0) and cin2 * kt2 >= 64:
+        return None      # m2 is a conv1d for the im2col + GEMM path
+    # ... and the kernels themselves, asked before anything is launched or looked up: the producer writes planes only from its
+    # shared-window kernel (long inputs), and once it has there is no float32 tensor for the consumer's other kernels
+    lib = _lib.load()
+    if not (lib.ms_maskconv_fwin_planes_supported(n, tin1, cout1, fout1, tout1, kf1, kt1, sf1, st1, dt1)
+            and lib.ms_maskconv_cl_supported(n, cin2, fout1, cout2, fout2, tout2, kt2, st2, dt2)):
+        return None
+    _mask_in_place(acts, seq_lens)
+    x4 = _lib.f32c(acts)
+    host0 = _lib.host_lens(seq_lens).to(seq_lens.dtype)
+    host1 = out_lens(host0, kt1, st1, dt1, sum(pt1))
+    host2 = out_lens(host1, kt2, st2, dt2, sum(pt2))
+    pk1, pk2 = m1._packed.get_fwin(w1), m2._packed.get_cl(w2)
+    nbytes1 = lib.ms_maskconv_fwin_workspace_bytes(n, tin1, kf1, sf1, fout1)
+    ws1 = m1._packed.workspace.get(nbytes1)
+    planes = m2._packed.workspace.get(lib.ms_maskconv_cl_workspace_bytes(n, cin2, fout1, tout1))
+    b1 = None if m1.bias is None else _lib.f32c(m1.bias.detach())
+    b2 = None if m2.bias is None else _lib.f32c(m2.bias.detach())
+    lens0_dev = _lib.lens_i32(seq_lens)
+    _lib.check(lib.ms_maskconv_fwin_planes_forward(_lib.ptr(x4), _lib.ptr(lens0_dev), _lib.ptr(pk1), _lib.ptr(b1),
+                                                   _lib.ptr(planes), planes.numel(), n, fin1, tin1, cout1, fout1, tout1, kf1,
+                                                   kt1, sf1, st1, dt1, pf1[0], pt1[0], _lib.ACT_CLAMP, act1[0], act1[1],
+                                                   _lib.ptr(ws1), nbytes1, _lib.stream_ptr()),
+               "ms_maskconv_fwin_planes_forward")
+    lens1_dev = _lib.upload(host1, torch.int32)
+    y = torch.empty((n, cout2, fout2, tout2), dtype=torch.float32, device="cuda")
+    a2, lo2, hi2 = (_lib.ACT_NONE, 0.0, 0.0) if act2 is None else (_lib.ACT_CLAMP, act2[0], act2[1])
+    _lib.check(lib.ms_maskconv_cl_planes_forward(_lib.ptr(lens1_dev), _lib.ptr(pk2), _lib.ptr(b2), _lib.ptr(y), n, cin2, fout1,
+                                                 tout1, cout2, fout2, tout2, kf2, kt2, sf2, st2, df2, dt2, pf2[0], pt2[0], a2,
+                                                 lo2, hi2, _lib.ptr(planes), planes.numel(), _lib.stream_ptr()),
+               "ms_maskconv_cl_planes_forward")
+    return y, _lib.attach_host(_lib.upload(host2), host2)
 
 
 def _mask_in_place(acts: torch.Tensor, seq_lens: torch.Tensor):

@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from myrtlespeech_amd import _lib
-from myrtlespeech_amd.model.cnn import Conv1dTo2d, Conv2dTo1d, MaskConv1d, MaskConv2d
+from myrtlespeech_amd.model.cnn import Conv1dTo2d, Conv2dTo1d, MaskConv1d, MaskConv2d, conv_pair_forward
 from myrtlespeech_amd.model.fully_connected import FullyConnected, linear_stack_plan, run_linear_stack
 from myrtlespeech_amd.model.lookahead import Lookahead, lookahead_apply
 from myrtlespeech_amd.model.rnn import RNNState
@@ -28,6 +28,10 @@ from myrtlespeech_amd.model.utils import activation_clamp
 def _is_plain_activation(m) -> bool:
     return (isinstance(m, SeqLenWrapper) and isinstance(m.module, (torch.nn.Hardtanh, torch.nn.ReLU, torch.nn.Identity))
             and isinstance(m.seq_lens_fn, torch.nn.Identity))
+
+
+def _is_plain_clamp(m) -> bool:
+    return _is_plain_activation(m) and isinstance(m.module, (torch.nn.Hardtanh, torch.nn.ReLU))
 
 
 class DeepSpeech2(torch.nn.Module):
@@ -51,6 +55,16 @@ class DeepSpeech2(torch.nn.Module):
         i = 0
         while i < len(mods):
             m = mods[i]
+            if (isinstance(m, MaskConv2d) and i + 2 < len(mods) and _is_plain_clamp(mods[i + 1])
+                    and isinstance(mods[i + 2], MaskConv2d)):
+                # conv -> clamp -> conv (DS2's front end): the first hands the second its operand planes where the kernels allow
+                act2 = i + 3 < len(mods) and _is_plain_activation(mods[i + 3])
+                out = conv_pair_forward(m, activation_clamp(mods[i + 1].module), mods[i + 2],
+                                        activation_clamp(mods[i + 3].module) if act2 else None, h)
+                if out is not None:
+                    h = out
+                    i += 4 if act2 else 3
+                    continue
             if isinstance(m, (MaskConv1d, MaskConv2d)) and i + 1 < len(mods) and _is_plain_activation(mods[i + 1]):
                 h = m(h, fused_activation=activation_clamp(mods[i + 1].module))
                 i += 2

@@ -238,6 +238,16 @@ class TwoBatchesInFlight(BatchesInFlight):
         super().__init__(model, post=post, pre=pre, depth=2)
 
 
+def _index_to(index: torch.Tensor, dev: torch.device) -> torch.Tensor:
+    """A small host index tensor on the cuda device ``dev``, pinned and non-blocking (``_lib.upload``): a pageable ``.to``
+    blocks the host until the device has run everything queued before it, so the device would run dry once at the start and
+    twice at the end of every pair's forward and the next kernels would be issued from a standing start.  (``_lib.upload``
+    targets the current device; inputs that live on another one get the plain copy.)"""
+    if dev.index in (None, torch.cuda.current_device()):
+        return _lib.upload(index)
+    return index.to(dev)
+
+
 class PairedBatches:
     """``PairedBatches(model)(batches)``: the other throughput mode (round 3) -- consecutive batches go through ``model`` two at
     a time as ONE batch.  For the config-2 network (5 x BiLSTM-1024, batches of 32) the library then runs the two batches'
@@ -294,7 +304,7 @@ class PairedBatches:
                 where = torch.empty_like(order)
                 where[order] = torch.arange(order.numel())                               # source row -> merged position
                 dev = xa.device if xa.is_cuda else torch.device("cuda")
-                order_d = order.to(dev)
+                order_d = _index_to(order, dev)
                 x = torch.cat([xa.to(dev), xb.to(dev)]).index_select(0, order_d)
                 lens = both[order].to(la.dtype)
                 if self.pre is not None:
@@ -302,7 +312,7 @@ class PairedBatches:
                     self.pre(k + 1)
                 (y, out_lens), hid = self.model((x, lens))
                 if bool((both < xa.shape[-1]).any()):                                    # the reference masks its input in place
-                    back = x.index_select(0, where.to(dev))
+                    back = x.index_select(0, _index_to(where, dev))
                     if xa.is_cuda:
                         xa.copy_(back[:na])
                     if xb.is_cuda:
@@ -310,7 +320,7 @@ class PairedBatches:
                 out_host = _lib.host_lens(out_lens)
                 for b, (lo, hi) in enumerate(((0, na), (na, both.numel()))):
                     pos = where[lo:hi]
-                    pos_d = pos.to(dev)
+                    pos_d = _index_to(pos, dev)
                     lens_b = out_host[pos].to(out_lens.dtype)
                     lens_b = _lib.attach_host(_lib.upload(lens_b), lens_b) if out_lens.is_cuda else lens_b
                     if isinstance(hid, tuple):
