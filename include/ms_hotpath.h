@@ -762,6 +762,63 @@ int ms_rnnt_score(const float* enc_p, const float* pred_p, const float* w_out, c
                   const int32_t* targets, const int32_t* tgt_lens, float* nll, float* lattice, int N, int T, int U1, int J,
                   int V1, int blank, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The fused transducer loss WITH its gradient: ms_rnnt_score's forward plus a Z plane, and a backward with respect to
+ *      enc_p, pred_p, w_out and b_out that never holds a V1-wide row per cell for the whole lattice.  OWN specification;
+ *      restated in numpy by tests/rnnt_joint_loss_ref.py on top of tests/rnnt_loss_ref.py and tests/rnnt_score_ref.py.
+ *
+ * Forward.  ms_rnnt_joint_loss_forward takes ms_rnnt_score's arguments (its workspace is ms_rnnt_score_workspace_bytes) and
+ * runs the same three launches; lattice is float32 [3][N][T][U1] = Z, alpha, beta as for ms_rnnt_loss_forward
+ * (ms_rnnt_joint_loss_lattice_bytes = 12 N T U1), Z = NaN in a cell whose Z is not finite.  nll, alpha and beta are
+ * ms_rnnt_score's bit for bit.
+ *
+ * Backward.  For an existing cell c = (n, t, u), t < T_n, u <= U_n:
+ *   h_c = tanh(enc_p[t, n] + pred_p[u, n]);   x_c = w_out h_c + b_out;   Z, b, e, alpha, beta, ll as for ms_rnnt_loss_forward
+ * and the gradient of sum_n grad_nll[n] nll[n] is
+ *   g_c[v]  = grad_nll[n] ( exp(x_c[v] - Z_c + alpha_c + beta_c - ll_n)
+ *                           - [v == blank] exp(alpha_c + b_c + beta(t+1, u) - ll_n)     (at (T_n-1, U_n): exp(alpha + b - ll);
+ *                                                                                        at every other (T_n-1, u): 0)
+ *                           - [u < U_n, v == y_u] exp(alpha_c + e_c + beta(t, u+1) - ll_n) )
+ *   d_b_out[v]      = sum_c g_c[v]
+ *   d_w_out[v, j]   = sum_c g_c[v] h_c[j]
+ *   da_c[j]         = (sum_v g_c[v] w_out[v, j]) (1 - h_c[j]^2)
+ *   d_enc_p[t, n]   = sum_{u <= U_n} da_(n,t,u)
+ *   d_pred_p[u, n]  = sum_{t < T_n} da_(n,t,u)
+ * Edge cases mirror the loss.  An utterance with nll = +inf (an impossible transcript, the caller's errors in lengths or
+ * labels) contributes nothing to any gradient.  A NaN utterance: its own existing rows of d_enc_p and d_pred_p are NaN, and
+ * so are d_w_out and d_b_out (they are shared across utterances); every other utterance's rows stay clean.  Rows t >= T_n of
+ * d_enc_p[:, n] and rows u > U_n of d_pred_p[:, n] are written as 0; what lies in those INPUT rows and in targets past U_n
+ * changes no output bit.  All four gradients are always fully written.  d_b_out may be NULL (not wanted); b_out NULL: zeros.
+ *
+ * Arithmetic.  The three products -- the recomputed x = H w_out^T, dH = G w_out and d_w_out = G^T H -- are f16x3 on MFMA
+ * (both operands split into fp16 hi + lo, three products, float32 accumulation), whatever MS_PRECISION says.  The logits are
+ * recomputed with the forward's planes and K order: they are the forward's bit for bit.  G is split as 2^12 g and the scale
+ * undone in the epilogues; the error bound (tests/test_rnnt_joint_loss_gpu.py) is stated for |w_out| within [2^-10, 2^10]
+ * and |grad_nll| within [2^-10, 8].
+ *
+ * Memory.  The backward walks the cells in BANDS of units (8 frames of one utterance, every prediction row): per band row
+ * it holds g twice (row-major and transposed) and h once as fp16 hi + lo, and da as float32 -- 8 (V1p + Jp) bytes, V1p and
+ * Jp = V1 and J rounded up to 128 -- plus w_out packed twice and the partial sums of the d_w_out product, whose K extent is
+ * split over workgroups (up to 64 x V1p x Jp floats).  ms_rnnt_joint_loss_backward_workspace_min_bytes is one unit,
+ * ms_rnnt_joint_loss_backward_workspace_bytes the preferred size (as many units as fit in 500e6 bytes, at least one);
+ * any 16-byte aligned workspace of at least the minimum is accepted, MS_ERR_WORKSPACE below it.  A larger one only buys
+ * larger bands.  The size queries are host arithmetic in size_t and return 0 for non-positive shapes.
+ * Supported: U1 <= 1024 (and N T U1 < 2^33 cells), as the scorer; MS_ERR_UNSUPPORTED beyond, nothing launched.
+ * Neither call synchronises or allocates.  Sums across bands are stream-ordered launches, sums inside a band run in a fixed
+ * order; no atomics, no workgroup waits on another: the same inputs and the same workspace size give the same bits
+ * (different workspace sizes may differ in rounding). */
+size_t ms_rnnt_joint_loss_lattice_bytes(int N, int T, int U1);
+int ms_rnnt_joint_loss_forward(const float* enc_p, const float* pred_p, const float* w_out, const float* b_out,
+                               const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens, float* nll,
+                               float* lattice, int N, int T, int U1, int J, int V1, int blank, void* workspace,
+                               size_t workspace_bytes, void* stream);
+size_t ms_rnnt_joint_loss_backward_workspace_min_bytes(int N, int T, int U1, int J, int V1);
+size_t ms_rnnt_joint_loss_backward_workspace_bytes(int N, int T, int U1, int J, int V1);
+int ms_rnnt_joint_loss_backward(const float* enc_p, const float* pred_p, const float* w_out, const float* b_out,
+                                const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens, const float* nll,
+                                const float* lattice, const float* grad_nll, float* d_enc_p, float* d_pred_p, float* d_w_out,
+                                float* d_b_out, int N, int T, int U1, int J, int V1, int blank, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

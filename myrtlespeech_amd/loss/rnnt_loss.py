@@ -14,6 +14,11 @@ With ``RNNT.joint_lattice`` the ``none`` reduction scores a transcript under a m
 ``rnnt_score`` is the same -log P without the logits: it takes the joint network's two projected inputs and its output layer,
 and ``ms_rnnt_score`` forms each cell's row inside one MFMA kernel, keeping only the two numbers per cell the recursion needs
 (``RNNT.transcript_nll`` builds it from a model).  No gradient.
+
+``rnnt_joint_loss`` / ``RNNTJointLoss`` is that scorer as a LOSS: the same forward value, and an autograd node whose backward
+(``ms_rnnt_joint_loss_backward``) gives the gradients of enc_p, pred_p, w_out and b_out without a ``[N, T, U + 1, V + 1]``
+tensor.  It differentiates the joint network only: the predictor and the encoder have no backward in this project, so
+training the whole ``RNNT`` module is out of scope.
 """
 from typing import Tuple
 
@@ -163,15 +168,10 @@ def check_score_shapes(t, n, u1, j, v1, in_lens, targets, target_lens, blank):
     return xl, yl
 
 
-def rnnt_score(enc_p: torch.Tensor, pred_p: torch.Tensor, w_out: torch.Tensor, b_out, in_lens: torch.Tensor,
-               targets: torch.Tensor, target_lens: torch.Tensor, blank: int, return_lattice: bool = False):
-    """``nll[N] = -log P(y_n | audio_n)`` from the joint network's inputs -- ``ms_rnnt_score`` (include/ms_hotpath.h).
-
-    enc_p [T, N, J] projected encoder frames, pred_p [U + 1, N, J] projected predictor outputs (row u: after ``y_n[:u]``),
-    w_out [V + 1, J] and b_out [V + 1] (or None) the joint's output layer, targets [N, U] padded labels.  The logits
-    ``w_out . tanh(enc_p[t] + pred_p[u]) + b_out`` are never stored: memory is 8 bytes per cell plus the packed weights.
-    Returns nll, or ``(nll, lattice)`` with lattice [2, N, T, U + 1] = alpha, beta (defined on existing cells only).
-    Detached float32 device tensors; there is no backward."""
+def _score_inputs(enc_p, pred_p, w_out, b_out, in_lens, targets, target_lens, blank):
+    """What ``rnnt_score`` and ``rnnt_joint_loss`` share: the validation (ValueError before a device is needed), the float32
+    device tensors and ONE staged upload for what starts on the host (RNNTLoss.forward).  Returns the tensors as given
+    to the kernels (detached) and the shape."""
     for name, x in (("enc_p", enc_p), ("pred_p", pred_p)):
         if not isinstance(x, torch.Tensor) or x.dim() != 3:
             raise ValueError(f"{name} must be [rows, batch, joint features]")
@@ -187,10 +187,8 @@ def rnnt_score(enc_p: torch.Tensor, pred_p: torch.Tensor, w_out: torch.Tensor, b
         raise ValueError(f"b_out must be [{v1}], got {tuple(b_out.shape)}")
     xl, yl = check_score_shapes(t, n, u1, j, v1, in_lens, targets, target_lens, blank)
     _lib.require_gpu()
-    lib = _lib.load()
     enc_p, pred_p, w = _lib.f32c(enc_p.detach()), _lib.f32c(pred_p.detach()), _lib.f32c(w_out.detach())
     b = None if b_out is None else _lib.f32c(b_out.detach())
-    # ONE staged upload for what starts on the host (RNNTLoss.forward)
     host_parts = [xl.to(torch.int32), yl.to(torch.int32)]
     y_on_host = not targets.is_cuda
     if y_on_host and targets.numel():
@@ -203,6 +201,14 @@ def rnnt_score(enc_p: torch.Tensor, pred_p: torch.Tensor, w_out: torch.Tensor, b
         y_dev = packed[2 * n:]
     else:
         y_dev = targets.detach().to(dtype=torch.int32).contiguous().reshape(-1)
+    return (enc_p, pred_p, w, b, xl_dev, y_dev, yl_dev), (n, t, u1, j, v1)
+
+
+def _run_score(args, shape, blank):
+    """``ms_rnnt_score``: nll [N] and lattice [2, N, T, U + 1]."""
+    enc_p, pred_p, w, b, xl_dev, y_dev, yl_dev = args
+    n, t, u1, j, v1 = shape
+    lib = _lib.load()
     nll = torch.empty(n, dtype=torch.float32, device="cuda")
     lattice = torch.empty((2, n, t, u1), dtype=torch.float32, device="cuda")
     nbytes = lib.ms_rnnt_score_workspace_bytes(n, t, u1, j, v1)
@@ -210,4 +216,116 @@ def rnnt_score(enc_p: torch.Tensor, pred_p: torch.Tensor, w_out: torch.Tensor, b
     _lib.check(lib.ms_rnnt_score(_lib.ptr(enc_p), _lib.ptr(pred_p), _lib.ptr(w), _lib.ptr(b), _lib.ptr(xl_dev), _lib.ptr(y_dev),
                                  _lib.ptr(yl_dev), _lib.ptr(nll), _lib.ptr(lattice), n, t, u1, j, v1, int(blank), _lib.ptr(ws),
                                  ws.numel(), _lib.stream_ptr()), "ms_rnnt_score")
+    return nll, lattice
+
+
+def rnnt_score(enc_p: torch.Tensor, pred_p: torch.Tensor, w_out: torch.Tensor, b_out, in_lens: torch.Tensor,
+               targets: torch.Tensor, target_lens: torch.Tensor, blank: int, return_lattice: bool = False):
+    """``nll[N] = -log P(y_n | audio_n)`` from the joint network's inputs -- ``ms_rnnt_score`` (include/ms_hotpath.h).
+
+    enc_p [T, N, J] projected encoder frames, pred_p [U + 1, N, J] projected predictor outputs (row u: after ``y_n[:u]``),
+    w_out [V + 1, J] and b_out [V + 1] (or None) the joint's output layer, targets [N, U] padded labels.  The logits
+    ``w_out . tanh(enc_p[t] + pred_p[u]) + b_out`` are never stored: memory is 8 bytes per cell plus the packed weights.
+    Returns nll, or ``(nll, lattice)`` with lattice [2, N, T, U + 1] = alpha, beta (defined on existing cells only).
+    Detached float32 device tensors; there is no backward."""
+    args, shape = _score_inputs(enc_p, pred_p, w_out, b_out, in_lens, targets, target_lens, blank)
+    nll, lattice = _run_score(args, shape, blank)
     return (nll, lattice) if return_lattice else nll
+
+
+class _RNNTJointLossFunction(torch.autograd.Function):
+    """Forward = ``ms_rnnt_joint_loss_forward`` (nll per utterance, the [3, N, T, U + 1] lattice saved); backward =
+    ``ms_rnnt_joint_loss_backward`` with its preferred workspace, gradients for exactly the inputs that require one."""
+
+    @staticmethod
+    def forward(ctx, enc_p, pred_p, w_out, b_out, args, shape, blank):
+        e, p, w, b, xl_dev, y_dev, yl_dev = args
+        n, t, u1, j, v1 = shape
+        lib = _lib.load()
+        nll = torch.empty(n, dtype=torch.float32, device="cuda")
+        lattice = torch.empty((3, n, t, u1), dtype=torch.float32, device="cuda")
+        nbytes = lib.ms_rnnt_score_workspace_bytes(n, t, u1, j, v1)
+        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device="cuda")         # transient: nothing outlives the call
+        _lib.check(lib.ms_rnnt_joint_loss_forward(_lib.ptr(e), _lib.ptr(p), _lib.ptr(w), _lib.ptr(b), _lib.ptr(xl_dev),
+                                                  _lib.ptr(y_dev), _lib.ptr(yl_dev), _lib.ptr(nll), _lib.ptr(lattice), n, t, u1, j,
+                                                  v1, int(blank), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "ms_rnnt_joint_loss_forward")
+        saved = [e, p, w, nll, lattice] + ([b] if b is not None else [])
+        ctx.save_for_backward(*saved)
+        ctx.meta = dict(shape=shape, blank=int(blank), xl_dev=xl_dev, y_dev=y_dev, yl_dev=yl_dev, has_bias=b is not None,
+                        like=(enc_p, pred_p, w_out, b_out))
+        return nll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        e, p, w, nll, lattice = ctx.saved_tensors[:5]
+        m = ctx.meta
+        b = ctx.saved_tensors[5] if m["has_bias"] else None
+        n, t, u1, j, v1 = m["shape"]
+        lib = _lib.load()
+        grad_nll = _lib.f32c(grad_out).reshape(n).contiguous()
+        d_e, d_p, d_w = torch.empty_like(e), torch.empty_like(p), torch.empty_like(w)
+        want_b = b is not None and ctx.needs_input_grad[3]
+        d_b = torch.empty_like(b) if want_b else None
+        nbytes = lib.ms_rnnt_joint_loss_backward_workspace_bytes(n, t, u1, j, v1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")                   # transient
+        _lib.check(lib.ms_rnnt_joint_loss_backward(
+            _lib.ptr(e), _lib.ptr(p), _lib.ptr(w), _lib.ptr(b), _lib.ptr(m["xl_dev"]), _lib.ptr(m["y_dev"]), _lib.ptr(m["yl_dev"]),
+            _lib.ptr(nll), _lib.ptr(lattice), _lib.ptr(grad_nll), _lib.ptr(d_e), _lib.ptr(d_p), _lib.ptr(d_w), _lib.ptr(d_b),
+            n, t, u1, j, v1, m["blank"], _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "ms_rnnt_joint_loss_backward")
+        grads = []
+        for k, (g, like) in enumerate(zip((d_e, d_p, d_w, d_b), m["like"])):
+            if g is None or not ctx.needs_input_grad[k]:
+                grads.append(None)
+            else:
+                grads.append(g.to(device=like.device, dtype=like.dtype).reshape(like.shape))
+        return (*grads, None, None, None)
+
+
+def rnnt_joint_loss(enc_p: torch.Tensor, pred_p: torch.Tensor, w_out: torch.Tensor, b_out, in_lens: torch.Tensor,
+                    targets: torch.Tensor, target_lens: torch.Tensor, blank: int, reduction: str = "mean"):
+    """The transducer loss from the joint network's INPUTS, differentiable: ``rnnt_score``'s value (its arguments, its
+    validation, its staged upload) under ``RNNTLoss``'s reductions (``none``: nll [N]; ``sum``; ``mean``: the sum divided by
+    the batch size N), as an autograd node over enc_p [T, N, J], pred_p [U + 1, N, J], w_out [V + 1, J] and b_out [V + 1]
+    (or None).  The node saves the inputs, nll and the [3, N, T, U + 1] lattice (Z, alpha, beta) -- 12 bytes per cell; its
+    backward is ``ms_rnnt_joint_loss_backward`` (include/ms_hotpath.h) with its preferred workspace and returns gradients
+    for exactly the inputs that require one.  No ``[N, T, U + 1, V + 1]`` tensor exists at any point.  With grad disabled, or
+    when no input requires grad, it makes ``rnnt_score``'s launches only.
+
+    It differentiates the joint network's output layer and its two projected inputs.  The predictor and the encoder have
+    no backward in this project: training the whole ``RNNT`` module is out of scope."""
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"{reduction} is not a valid value for reduction")
+    args, shape = _score_inputs(enc_p, pred_p, w_out, b_out, in_lens, targets, target_lens, blank)
+    inputs = (enc_p, pred_p, w_out) + (() if b_out is None else (b_out,))
+    if torch.is_grad_enabled() and any(x.requires_grad for x in inputs):
+        nll = _RNNTJointLossFunction.apply(enc_p, pred_p, w_out, b_out, args, shape, int(blank))
+    else:
+        nll = _run_score(args, shape, blank)[0]
+    if reduction == "none":
+        return nll
+    total = nll.sum()
+    return total if reduction == "sum" else total / shape[0]
+
+
+class RNNTJointLoss(torch.nn.Module):
+    """``rnnt_joint_loss`` as a module: ``loss((enc_p, in_lens), pred_p, w_out, b_out, (targets, target_lens))``."""
+
+    def __init__(self, blank: int, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in _REDUCTIONS:
+            raise ValueError(f"{reduction} is not a valid value for reduction")
+        if int(blank) < 0:
+            raise ValueError(f"blank={blank} must be >= 0")
+        self.blank = int(blank)
+        self.reduction = reduction
+
+    def extra_repr(self) -> str:
+        return f"blank={self.blank}, reduction={self.reduction}"
+
+    def forward(self, inputs: Tuple[torch.Tensor, torch.Tensor], pred_p: torch.Tensor, w_out: torch.Tensor, b_out,
+                targets: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        enc_p, in_lens = inputs
+        y, y_lens = targets
+        return rnnt_joint_loss(enc_p, pred_p, w_out, b_out, in_lens, y, y_lens, self.blank, self.reduction)
