@@ -819,6 +819,67 @@ int ms_rnnt_joint_loss_backward(const float* enc_p, const float* pred_p, const f
                                 float* d_b_out, int N, int T, int U1, int J, int V1, int blank, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* ---- Transducer forced alignment: the best path of a GIVEN transcript through the lattice, i.e. the Viterbi (max-plus)
+ *      form of the recursion ms_rnnt_loss_forward sums, its back-trace, and where every label is emitted.  OWN
+ *      specification; restated in numpy by tests/rnnt_align_ref.py.
+ *
+ * Per utterance n the existing cells are t < T_n, u <= U_n; b(t,u) = lp(t,u,blank) and e(t,u) = lp(t,u,y_u) (u < U_n) exactly
+ * as in the comment on ms_rnnt_loss_forward.  Recursion in natural-log float32, one rounding per addition and no other
+ * arithmetic:
+ *   d(0,0) = 0
+ *   d(t,u): best = d(t-1,u) + b(t-1,u), k = 0                          (absent when t == 0)
+ *           if u >= 1 and d(t,u-1) + e(t,u-1) > best (strictly, or when the blank predecessor is absent):
+ *               best = that value, k = 1
+ *           d(t,u) = best, back-pointer k        -- a tie takes the blank predecessor
+ *   score = d(T_n-1, U_n) + b(T_n-1, U_n)
+ * and the path is found by walking the back-pointers from (T_n-1, U_n) to (0,0).
+ *
+ * Edge cases.
+ *   an impossible transcript (a -inf makes score = -inf): no path; every per-frame and per-token integer output is -1, every
+ *     log-probability output of the utterance's own frames and labels -inf.
+ *   a NaN or +inf b or e in an existing cell, or a non-finite normaliser of one: score = NaN for that utterance only; no path;
+ *     the integer outputs are -1, the log-probability outputs NaN.
+ *   T_n outside [1, T], U_n outside [0, U1 - 1], a label outside [0, V1) or equal to blank: the caller's error; nothing is read
+ *     out of bounds for it; score = -inf and no path (frames and labels counted with the lengths clamped to the shapes).
+ *   what lies in cells that do not exist and in targets past U_n changes no output bit.
+ *
+ * Outputs, always fully written:
+ *   score       [N] float32           the score of the best path
+ *   token_frame [N, U1 - 1] int32     the frame t at which label u is emitted (the step (t,u) -> (t,u+1)); -1 for u >= U_n
+ *   token_logp  [N, U1 - 1] float32   e(token_frame[u], u); 0 for u >= U_n
+ *   frame_u     [N, T] int32          the u at which the path takes the blank of frame t = the number of labels emitted through
+ *                                     frame t; -1 for t >= T_n
+ *   frame_logp  [N, T] float32        b(t, frame_u[t]); 0 for t >= T_n
+ * (targets and the two token outputs may be NULL when U1 == 1).  score is, bit for bit, the float32 sum of those
+ * log-probabilities in path order starting from 0: for each frame its emitted labels in order of u, then its blank.
+ *
+ * ms_rnnt_align takes logits [N, T, U1, V1] as the loss does.  flags = 0: logits in, the device runs the loss's own
+ * normaliser pass (its Z goes to workspace scratch).  flags = MS_RNNT_LOG_PROBS_IN: b and e are x[n,t,u,blank] and
+ * x[n,t,u,y_u] exactly as given (-inf is allowed and means "impossible").
+ * ms_rnnt_align_joint takes ms_rnnt_score's inputs (enc_p, pred_p, w_out, b_out; see there) and runs its pack and cells
+ * launches: there is no [N, T, U1, V1] tensor, and b, e carry the error bound of ms_rnnt_score.
+ *
+ * Memory.  d lives in registers: there is no alpha / beta lattice.  The back-pointer of a cell is one bit; a diagonal t + u of
+ * an utterance is ceil(U1 / 64) 64-bit words, an utterance (T + U1 - 1) such rows: in LDS while they fit
+ * MS_RNNT_ALIGN_BP_LDS_BYTES, else in the workspace.  ms_rnnt_align_workspace_bytes = the two skewed planes of the loss + Z
+ * scratch of N T U1 floats; ms_rnnt_align_joint_workspace_bytes = ms_rnnt_score_workspace_bytes; each rounded up to 256
+ * bytes and grown by the N utterances' back-pointer rows exactly when they leave the LDS.  The workspace must be 16-byte
+ * aligned and is transient.  The size queries are host arithmetic and return 0 for non-positive shapes.
+ * Supported: the shapes of ms_rnnt_loss_forward / ms_rnnt_score (U1 <= 1024); MS_ERR_UNSUPPORTED beyond, nothing launched.
+ * Neither call synchronises nor allocates.  Two launches (planes; walk, back-trace and read-out: a workgroup per utterance),
+ * three for the joint form; no workgroup waits on another, no atomics, no status word: the same inputs give the same bits. */
+#define MS_RNNT_LOG_PROBS_IN 2
+#define MS_RNNT_ALIGN_BP_LDS_BYTES 98304
+size_t ms_rnnt_align_workspace_bytes(int N, int T, int U1, int V1);
+int ms_rnnt_align(const float* logits, const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens, float* score,
+                  int32_t* token_frame, float* token_logp, int32_t* frame_u, float* frame_logp, int N, int T, int U1, int V1,
+                  int blank, int flags, void* workspace, size_t workspace_bytes, void* stream);
+size_t ms_rnnt_align_joint_workspace_bytes(int N, int T, int U1, int J, int V1);
+int ms_rnnt_align_joint(const float* enc_p, const float* pred_p, const float* w_out, const float* b_out, const int32_t* in_lens,
+                        const int32_t* targets, const int32_t* tgt_lens, float* score, int32_t* token_frame, float* token_logp,
+                        int32_t* frame_u, float* frame_logp, int N, int T, int U1, int J, int V1, int blank, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,10 @@ SIGNATURES = {
     "ms_rnnt_joint_loss_backward_workspace_min_bytes": (c_size_t, [c_int] * 5),
     "ms_rnnt_joint_loss_backward_workspace_bytes": (c_size_t, [c_int] * 5),
     "ms_rnnt_joint_loss_backward": (c_int, [_P] * 14 + [c_int] * 6 + [_P, c_size_t, _P]),
+    "ms_rnnt_align_workspace_bytes": (c_size_t, [c_int] * 4),
+    "ms_rnnt_align": (c_int, [_P] * 9 + [c_int] * 6 + [_P, c_size_t, _P]),
+    "ms_rnnt_align_joint_workspace_bytes": (c_size_t, [c_int] * 5),
+    "ms_rnnt_align_joint": (c_int, [_P] * 12 + [c_int] * 6 + [_P, c_size_t, _P]),
     "ms_mfcc_workspace_bytes": (c_size_t, [c_int] * 5),
     "ms_mfcc_forward": (c_int, [_P] * 7 + [c_int] * 7 + [c_float, _P, c_size_t, _P]),
     "ms_mfcc_legacy_forward": (c_int, [_P] * 7 + [c_int] * 8 + [c_double, _P]),

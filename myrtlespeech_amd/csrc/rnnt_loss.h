@@ -1,5 +1,6 @@
-// What the transducer loss (rnnt_loss.hip) and the fused scorer (rnnt_score.hip) share: the layout of the two skewed planes
-// b = lp(blank), e = lp(y_u), the tests on lengths and labels, the supported shapes, and the launch of the lattice pass.
+// What the transducer loss (rnnt_loss.hip), the fused scorer (rnnt_score.hip) and the forced aligner (rnnt_align.hip) share:
+// the layout of the two skewed planes b = lp(blank), e = lp(y_u), the tests on lengths and labels, the supported shapes, and
+// the launches of the normaliser and the lattice pass.
 #pragma once
 #include <math.h>
 
@@ -36,5 +37,11 @@ static inline bool rl_supported(int N, int T, int U1) {
 int rnnt_lattice_launch(const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens, const float* b_sk,
                         const float* e_sk, float* alpha, float* beta, float* nll, int N, int T, int U1, int V1, int blank,
                         hipStream_t st);
+
+// The normaliser pass (rnnt_loss_normalise_kernel) alone: Z [N, T, U1] and the two skewed planes from logits [N, T, U1, V1].
+// What ms_rnnt_loss_forward launches first; ms_rnnt_align (rnnt_align.hip) runs it with Z in workspace scratch.
+// Enqueues on `st`; MS_OK or MS_ERR_HIP.
+int rnnt_normalise_launch(const float* logits, const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens, float* Z,
+                          float* b_sk, float* e_sk, int N, int T, int U1, int V1, int blank, hipStream_t st);
 
 }  // namespace ms

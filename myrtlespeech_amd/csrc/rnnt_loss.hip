@@ -334,6 +334,16 @@ int ms::rnnt_lattice_launch(const int32_t* in_lens, const int32_t* targets, cons
   return MS_OK;
 }
 
+int ms::rnnt_normalise_launch(const float* logits, const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens,
+                              float* Z, float* b_sk, float* e_sk, int N, int T, int U1, int V1, int blank, hipStream_t st) {
+  const long R = (long)((size_t)N * T * U1);
+  const bool vec = (V1 % 4 == 0) && rl_aligned16(logits);
+  RL_ROW_LAUNCH(rnnt_loss_normalise_kernel, R, V1, vec, st, logits, in_lens, targets, tgt_lens, Z, b_sk, e_sk, R, T, U1, V1,
+                blank);
+  MS_LAUNCH_CHECK();
+  return MS_OK;
+}
+
 extern "C" size_t ms_rnnt_loss_lattice_bytes(int N, int T, int U1) {
   if (N <= 0 || T <= 0 || U1 <= 0) return 0;
   return (size_t)3 * N * T * U1 * sizeof(float);
@@ -367,11 +377,8 @@ extern "C" int ms_rnnt_loss_forward(const float* logits, const int32_t* in_lens,
   float* beta = lattice + 2 * plane;
   float* b_sk = (float*)workspace;
   float* e_sk = (float*)((char*)workspace + ms::align_up((size_t)N * rl_skew_rows(T, U1) * U1 * sizeof(float), 256));
-  const long R = (long)plane;
-  const bool vec = (V1 % 4 == 0) && rl_aligned16(logits);
-  RL_ROW_LAUNCH(rnnt_loss_normalise_kernel, R, V1, vec, st, logits, in_lens, targets, tgt_lens, Z, b_sk, e_sk, R, T, U1, V1,
-                blank);
-  MS_LAUNCH_CHECK();
+  const int rc = ms::rnnt_normalise_launch(logits, in_lens, targets, tgt_lens, Z, b_sk, e_sk, N, T, U1, V1, blank, st);
+  if (rc != MS_OK) return rc;
   return ms::rnnt_lattice_launch(in_lens, targets, tgt_lens, b_sk, e_sk, alpha, beta, nll, N, T, U1, V1, blank, st);
 }
 

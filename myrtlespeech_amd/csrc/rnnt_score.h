@@ -34,11 +34,19 @@ int rnnt_score_launch(const float* enc_p, const float* pred_p, const float* w_ou
                       const int32_t* targets, const int32_t* tgt_lens, float* nll, float* Z, float* alpha, float* beta, int N,
                       int T, int U1, int J, int V1, int blank, void* workspace, hipStream_t st);
 
+// pack and cells alone, without the lattice pass: the two skewed planes (and Z, when asked) are left in the workspace laid
+// out as above.  What the forced aligner (rnnt_align.hip) runs its own walk on.
+int rnnt_score_cells_launch(const float* enc_p, const float* pred_p, const float* w_out, const float* b_out,
+                            const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens, float* Z, int N, int T,
+                            int U1, int J, int V1, int blank, void* workspace, hipStream_t st);
+
 // the shapes the launches serve: the loss's, and grids that fit 31 bits
 bool rnnt_score_supported(int N, int T, int U1, int J, int V1);
 
 }  // namespace ms
 
+// (rnnt_align.hip runs the launches above and has no use for the kernels: it defines RNNT_SCORE_DECLARATIONS_ONLY)
+#ifndef RNNT_SCORE_DECLARATIONS_ONLY
 namespace {
 
 using ms::f32x16;
@@ -375,3 +383,4 @@ __global__ __launch_bounds__(RS_THREADS) void rnnt_score_cells_kernel(
 }
 
 }  // namespace
+#endif  // RNNT_SCORE_DECLARATIONS_ONLY

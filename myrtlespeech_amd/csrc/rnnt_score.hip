@@ -44,9 +44,9 @@ using ms::rs_col_blocks;
 using ms::rs_k_steps;
 using ms::rs_packed_bytes;
 
-int ms::rnnt_score_launch(const float* enc_p, const float* pred_p, const float* w_out, const float* b_out, const int32_t* in_lens,
-                          const int32_t* targets, const int32_t* tgt_lens, float* nll, float* Z, float* alpha, float* beta,
-                          int N, int T, int U1, int J, int V1, int blank, void* workspace, hipStream_t st) {
+int ms::rnnt_score_cells_launch(const float* enc_p, const float* pred_p, const float* w_out, const float* b_out,
+                                const int32_t* in_lens, const int32_t* targets, const int32_t* tgt_lens, float* Z, int N, int T,
+                                int U1, int J, int V1, int blank, void* workspace, hipStream_t st) {
   const int tiles_t = ms::cdiv(T, RS_TT), tiles_u = ms::cdiv(U1, RS_TU);
   const long tiles = (long)N * tiles_t * tiles_u;
   const long pack_threads = (long)(rs_col_blocks(V1) * rs_k_steps(J) * 64);
@@ -67,6 +67,17 @@ int ms::rnnt_score_launch(const float* enc_p, const float* pred_p, const float* 
   else RS_CELLS(4);
 #undef RS_CELLS
   MS_LAUNCH_CHECK();
+  return MS_OK;
+}
+
+int ms::rnnt_score_launch(const float* enc_p, const float* pred_p, const float* w_out, const float* b_out, const int32_t* in_lens,
+                          const int32_t* targets, const int32_t* tgt_lens, float* nll, float* Z, float* alpha, float* beta,
+                          int N, int T, int U1, int J, int V1, int blank, void* workspace, hipStream_t st) {
+  const int rc = ms::rnnt_score_cells_launch(enc_p, pred_p, w_out, b_out, in_lens, targets, tgt_lens, Z, N, T, U1, J, V1, blank,
+                                             workspace, st);
+  if (rc != MS_OK) return rc;
+  const float* b_sk = (const float*)workspace;
+  const float* e_sk = (const float*)((const char*)workspace + ms::rl_skew_plane_bytes(N, T, U1));
   return ms::rnnt_lattice_launch(in_lens, targets, tgt_lens, b_sk, e_sk, alpha, beta, nll, N, T, U1, V1, blank, st);
 }
 

@@ -178,3 +178,43 @@ class RNNT(torch.nn.Module):
             pred_p = self.joint._linear(_lib.f32c(pred).reshape(u1 * n, -1), self.joint.pred_proj)   # [U1*N, J], row u*N + n
             return rnnt_score(enc_p.reshape(t, n, -1), pred_p.reshape(u1, n, -1), w.detach(), None if b is None else b.detach(),
                               lens, targets, target_lens, blank)
+
+    def align(self, enc: torch.Tensor, lens: torch.Tensor, targets: torch.Tensor, target_lens: torch.Tensor):
+        """Forced alignment of GIVEN transcripts, WITHOUT the logit lattice: enc [T, N, E] encoder frames, targets [N, U]
+        padded labels -> one ``post_process.rnnt_aligner.RNNTAlignment`` per utterance (the best path's score, the frame at
+        which every label is emitted, each frame's blank log-probability), ``None`` where the transcript cannot be aligned.
+        The plumbing of ``transcript_nll`` -- one projection of the encoder, ``forward_targets``, one projection of its output
+        -- then ``ms_rnnt_align_joint``: the scorer's pack and cells launches and the aligner's walk, whose memory does not
+        grow with the alphabet.  The same path as ``RNNTForcedAligner`` on ``joint_lattice`` wherever the best path leads by
+        more than the bounds of tests/test_rnnt_align_gpu.py.  Detached; one staged upload, one read-back."""
+        from myrtlespeech_amd.loss.rnnt_loss import _score_inputs, check_score_shapes
+        from myrtlespeech_amd.post_process import rnnt_aligner as A
+        if enc.dim() != 3 or targets.dim() != 2 or targets.shape[0] != enc.shape[1]:
+            raise ValueError(f"enc must be [T, N, E] and targets [N, U], got {tuple(enc.shape)} and {tuple(targets.shape)}")
+        t, n, _ = enc.shape
+        u1 = targets.shape[1] + 1
+        w, b = self.joint.out.weight, self.joint.out.bias
+        blank = self.predictor.blank
+        xl, yl = check_score_shapes(t, n, u1, w.shape[1], w.shape[0], lens, targets, target_lens, blank)
+        labels = A.validate_labels(targets, yl, w.shape[0], blank)
+        _lib.require_gpu()
+        lib = _lib.load()
+        with torch.no_grad():
+            enc_p = self.joint.project_encoder(enc.detach())                    # [T*N, J], row t*N + n
+            pred = self.predictor.forward_targets(targets, target_lens)         # [U1, N, H]
+            pred_p = self.joint._linear(_lib.f32c(pred).reshape(u1 * n, -1), self.joint.pred_proj)   # [U1*N, J], row u*N + n
+            args, shape = _score_inputs(enc_p.reshape(t, n, -1), pred_p.reshape(u1, n, -1), w.detach(),
+                                        None if b is None else b.detach(), lens, targets, target_lens, blank)
+            e, p, wd, bd, xl_dev, y_dev, yl_dev = args
+            j, v1 = shape[3], shape[4]
+            out, (score, t_frame, t_logp, f_u, f_logp), sizes = A.output_buffer(n, t, u1)
+            nbytes = lib.ms_rnnt_align_joint_workspace_bytes(n, t, u1, j, v1)
+            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device="cuda")     # transient: nothing outlives the call
+            has_tokens = u1 > 1
+            _lib.check(lib.ms_rnnt_align_joint(_lib.ptr(e), _lib.ptr(p), _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(xl_dev),
+                                               _lib.ptr(y_dev), _lib.ptr(yl_dev), _lib.ptr(score),
+                                               _lib.ptr(t_frame if has_tokens else None),
+                                               _lib.ptr(t_logp if has_tokens else None), _lib.ptr(f_u), _lib.ptr(f_logp), n, t,
+                                               u1, j, v1, int(blank), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "ms_rnnt_align_joint")
+        return A.read_back(out, sizes, labels, xl.tolist(), n, t, u1, "RNNT.align")
