@@ -13,7 +13,8 @@
  *   - every pointer is a DEVICE pointer unless its name ends in _host;
  *   - tensors are dense, row-major, float32 unless stated; lengths are int32;
  *   - `stream` is a hipStream_t (NULL = default stream); calls only enqueue
- *     work, they never synchronise (exceptions: ms_rnn_status, ms_prof_read and the greedy ms_rnnt_decode);
+ *     work, they never synchronise (exceptions: ms_rnn_status, ms_prof_read, the greedy ms_rnnt_decode and
+ *     ms_rnnt_greedy_stream_step);
  *   - return value: MS_OK or an MS_ERR_* code; ms_last_error() describes the
  *     last failure on the calling thread;
  *   - outputs are caller-allocated; nothing is freed or retained.
@@ -675,6 +676,59 @@ int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const float* embeddi
                    const float* w_out, const float* b_out, int32_t* out_idx, int32_t* out_len, float* out_score, int T,
                    int N, int V, int D, int H, int L, int J, int beam_width, int max_symbols, int greedy, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* The greedy decode advanced one chunk of encoder rows at a time (own specification: oracle/rnnt_oracle.py::greedy_decode
+ * with its frame loop cut BETWEEN frames; restated in numpy by tests/rnnt_stream_ref.py).  The predictor's LSTM state and the
+ * prefix it encodes survive the cut: everything a stream carries lives in `state`
+ * (ms_rnnt_greedy_stream_state_bytes(N, H, L, J) bytes of device memory, 16-byte aligned; host arithmetic, 0 for a
+ * non-positive shape): int32 words [0] the sticky overflow word, [1] iterations launched since _begin (a record for tools),
+ * [2 .. 15] reserved, then four per stream i at [16 + 4 i]: label count, frames seen, two reserved; then, each aligned to 256
+ * bytes, float32 h [N, L, H], c [N, L, H] (the predictor after the stream's prefix) and pred_p [N, J] = w_pred . h_top.
+ * Network arguments as ms_rnnt_decode takes them (blank = V); they must be the same in _begin and in every _step.
+ * `workspace`: ms_rnnt_greedy_stream_workspace_bytes(N, V, D, H, L, J) bytes, 16-byte aligned; nothing in it outlives a call,
+ * so _begin and the steps of several decoders may share one.
+ * _begin: clears the overflow word, sets every stream to zero labels, zero frames seen and zero h and c in every layer, takes
+ * the predictor step on the start symbol and stores the resulting state and its pred_p.  The start step is the same for every
+ * stream: it is computed once and broadcast.  Only enqueues.
+ * _step: enc_p [rows * n, J], row r n + i, are the next `rows` projected encoder frames of the first n <= N streams (streams
+ * leave a sorted batch as a suffix, as in ms_ctc_greedy_stream_step).  Rows that exist for stream i: chunk_lens[i] (clamped to
+ * [0, rows]) if chunk_lens is given, otherwise clamp(total_lens[i] - frames_seen[i], 0, rows); exactly one of the two is
+ * non-NULL.  frames_seen[i] advances by the rows that existed.  Per existing frame, in order: x = w_out . tanh(enc_p[row] +
+ * pred_p_i) + b_out; the symbol is the arg max over the LOGITS x (first maximum wins; a row without a number counts as blank);
+ * blank moves to the next frame; a label is appended, the stream's predictor takes one step on it (a new pred_p_i) and the same
+ * frame is scored again; after max_symbols labels on one frame the frame advances.  A frame never spans two steps, so nothing
+ * about the quota is carried.
+ * labels [N, cap]: appended at the stream's running label count; label_frames [N, cap] (may be NULL): the 0-based index,
+ * counted over the stream's existing rows since _begin, of the frame that emitted the label.  A stream that would exceed `cap`
+ * labels stops appending, keeps counting, sets the overflow word and keeps advancing its predictor, so later labels are still
+ * the right ones.  fresh [N, 1 + rows * max_symbols] (may be NULL): column 0 = labels this call appended for the stream (0 for
+ * streams n .. N-1), columns 1.. = those labels.
+ * Arithmetic: the joint's output layer as three fp16 MFMA products of hi + lo planes (f16x3, as ms_rnnt_score; MS_PRECISION is
+ * not consulted), the predictor in float32 FMA.  DETERMINISM is part of the contract: the logit row of a (frame, prefix) pair
+ * and the predictor state after a prefix are computed by the same sequence of operations wherever the rows are cut, wherever
+ * the frame sits among the 32 a stream has scored at once, and whichever other streams are in the batch; transcripts and
+ * label_frames of a clip are the same for every way of cutting it.
+ * Non-finite input: a NaN or infinity in an existing row of one stream leaves that stream's labels unspecified (they stay
+ * inside [0, V)); nothing is read or written out of bounds, the call ends within its bound, every other stream is unchanged.
+ * Like the greedy ms_rnnt_decode, _step BLOCKS the host: the number of iterations (score 32 pending frames per stream, step the
+ * predictor of the streams that emitted) depends on the labels, so the host polls a device counter of finished streams a few
+ * iterations behind the launch queue and returns once the last poll's copy has landed.  It runs at most rows * max_symbols +
+ * ceil(rows / 32) + 1 iterations whatever the device reports; no kernel waits on another workgroup (no spin, no status word).
+ * For the same reason a step CANNOT be captured into a HIP graph.  MS_ERR_HIP if the pinned counter ring cannot be created.
+ * Shapes: those of the greedy ms_rnnt_decode (at most 8 predictor layers) and any V and J; beyond them MS_ERR_UNSUPPORTED, and
+ * nothing is launched. */
+size_t ms_rnnt_greedy_stream_state_bytes(int N, int H, int L, int J);
+size_t ms_rnnt_greedy_stream_workspace_bytes(int N, int V, int D, int H, int L, int J);
+int ms_rnnt_greedy_stream_begin(void* state, int N, const float* embedding, const float* const* w_ih, const float* const* w_hh,
+                                const float* const* b_ih, const float* const* b_hh, const float* w_pred, const float* w_out,
+                                const float* b_out, int V, int D, int H, int L, int J, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int ms_rnnt_greedy_stream_step(const float* enc_p, int rows, int n, const int32_t* total_lens, const int32_t* chunk_lens,
+                               const float* embedding, const float* const* w_ih, const float* const* w_hh,
+                               const float* const* b_ih, const float* const* b_hh, const float* w_pred, const float* w_out,
+                               const float* b_out, int32_t* labels, int32_t* label_frames, int cap, int32_t* fresh, void* state,
+                               int N, int V, int D, int H, int L, int J, int max_symbols, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* ---- RNN-T (transducer) loss: forward, and the gradient with respect to the joint's logits.  OWN specification, like
  *      everything under the RNN-T label (the reference snapshot has no transducer; parity unpinned); restated in numpy by
