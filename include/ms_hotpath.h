@@ -934,6 +934,53 @@ int ms_rnnt_align_joint(const float* enc_p, const float* pred_p, const float* w_
                         int32_t* frame_u, float* frame_logp, int N, int T, int U1, int J, int V1, int blank, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- LSTM backward through time, and the embedding backward: what lets the transducer loss reach the prediction network.
+ *      OWN specification; restated in float64 numpy by tests/lstm_backward_ref.py.
+ *
+ * One layer of a unidirectional torch.nn.LSTM, float32 throughout, weights in torch layout and read as stored (no packed
+ * copy): w_ih [4H, In], w_hh [4H, H], b_ih / b_hh [4H] or NULL (zeros), gate order i, f, g, o:
+ *   a_t = x_t w_ih^T + b_ih + h_{t-1} w_hh^T + b_hh;   i, f, o = sigmoid(a_i, a_f, a_o);   g = tanh(a_g)
+ *   c_t = f c_{t-1} + i g;   h_t = o tanh(c_t)
+ * Any H, In, N, T >= 1.  lens [N] int32 on the device, sorted descending, or NULL (every sequence has T steps), with the
+ * forward's meaning: rows t >= lens[n] of the output are 0 and carry no gradient, h_n / c_n is the state at lens[n] - 1.
+ * lens is read on the device only; max_len = lens[0] (T without lens) is the number of steps the backward runs.
+ *
+ * ms_lstm_recompute.  The forward saves no gates; this call rebuilds them from x [T,N,In] and the forward's output
+ * h [T,N,H] (h0 / c0 [N,H], NULL = zeros).  Every h_{t-1} is known, so the pre-activations of all steps are two batch
+ * products over T N rows (the exact float32 MFMA GEMM behind ms_linear_forward) into the workspace
+ * (ms_lstm_recompute_workspace_bytes: two [T N, 4H] planes, each rounded up to 256 bytes; 0 for non-positive shapes), and
+ * a scan with exact expf / tanhf writes gates [T,N,4H] (activated: i, f, g, o) and c [T,N,H] for t < lens[n].  Rows past a
+ * length are not written, and nothing in them is read by ms_lstm_backward_steps.
+ *
+ * ms_lstm_backward_steps.  From gates, c, c0 (NULL = zeros), w_hh, d_out [T,N,H] (the gradient of the layer's output) and
+ * d_hn / d_cn [N,H] (the gradients of the final states; either may be NULL), for t = lens[n] - 1 down to 0:
+ *   dh_t = d_out[t] + dG_{t+1} w_hh  (+ d_hn at t == lens[n] - 1; no recurrent term there)
+ *   dc_t = dh_t o (1 - tanh(c_t)^2) + f_{t+1} dc_{t+1}  (d_cn in place of the last term at t == lens[n] - 1)
+ *   dG_t = [dc_t g i (1 - i), dc_t c_{t-1} f (1 - f), dc_t i (1 - g^2), dh_t tanh(c_t) o (1 - o)]
+ * Outputs, always fully written: dG [T,N,4H] = the gradient of the pre-activations, rows t >= lens[n] exact zeros;
+ * d_h0 = dG_0 w_hh and d_c0 = f_0 dc_0 [N,H] (d_c0 also carries dc between the steps); d_b [4H] = the column sums of dG.
+ * The batch products that finish the layer -- dx = dG w_ih, d_w_ih = dG^T x, d_w_hh = dG^T h_prev -- are ordinary GEMMs
+ * over T N rows and are left to ms_linear_forward.
+ * Launches: one per step from t = max_len - 1 down to 0, and one for d_h0; stream order is the only dependency between
+ * them -- no grid barrier, no spin wait, no persistent kernel.  A workgroup owns 32 hidden units for every n at every step,
+ * so d_b and dc are plain read-modify-writes: no atomics, the same inputs give the same bits.  The product is float32 MFMA
+ * (K = 4H), never split planes.  dG must be 16-byte aligned.  Neither call synchronises or allocates.
+ *
+ * ms_embedding_backward.  d_table[v, :] = the sum of d_out[r, :] over the rows r with clamp(idx[r], 0, V1 - 1) == v
+ * (ms_embedding_forward's clamping rule), added in the order of r by one workgroup per table row: deterministic bits,
+ * rows never looked up are written as zeros.  d_out [R, D], idx [R] int32, d_table [V1, D].
+ *
+ * Errors: NULL pointers (other than the optional ones above) and non-positive shapes MS_ERR_INVALID, a short workspace
+ * MS_ERR_WORKSPACE.  Out of scope: bidirectional layers, GRU / tanh cells, a single-launch recurrence, mixed precision. */
+size_t ms_lstm_recompute_workspace_bytes(int T, int N, int H);
+int ms_lstm_recompute(const float* x, const float* h, const float* h0, const float* c0, const int32_t* lens,
+                      const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* gates, float* c,
+                      int T, int N, int In, int H, void* workspace, size_t workspace_bytes, void* stream);
+int ms_lstm_backward_steps(const float* gates, const float* c, const float* c0, const float* w_hh, const float* d_out,
+                           const float* d_hn, const float* d_cn, const int32_t* lens, int max_len, float* dG, float* d_h0,
+                           float* d_c0, float* d_b, int T, int N, int H, void* stream);
+int ms_embedding_backward(const float* d_out, const int32_t* idx, float* d_table, int R, int D, int V1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

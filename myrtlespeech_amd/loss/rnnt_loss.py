@@ -17,8 +17,10 @@ and ``ms_rnnt_score`` forms each cell's row inside one MFMA kernel, keeping only
 
 ``rnnt_joint_loss`` / ``RNNTJointLoss`` is that scorer as a LOSS: the same forward value, and an autograd node whose backward
 (``ms_rnnt_joint_loss_backward``) gives the gradients of enc_p, pred_p, w_out and b_out without a ``[N, T, U + 1, V + 1]``
-tensor.  It differentiates the joint network only: the predictor and the encoder have no backward in this project, so
-training the whole ``RNNT`` module is out of scope.
+tensor.  It differentiates the joint network's output layer and its two projected inputs.  ``RNNT.loss`` (model/rnnt.py)
+carries those gradients on through the projections, the prediction network's LSTM (``model/rnn_autograd.py``) and its
+embedding, and to the encoder frames it was given; the encoder modules themselves (convolutions, bidirectional stacks, GRU)
+still have no backward in this project, so what trains is the predictor and the joint on a frozen encoder.
 """
 from typing import Tuple
 
@@ -293,8 +295,8 @@ def rnnt_joint_loss(enc_p: torch.Tensor, pred_p: torch.Tensor, w_out: torch.Tens
     for exactly the inputs that require one.  No ``[N, T, U + 1, V + 1]`` tensor exists at any point.  With grad disabled, or
     when no input requires grad, it makes ``rnnt_score``'s launches only.
 
-    It differentiates the joint network's output layer and its two projected inputs.  The predictor and the encoder have
-    no backward in this project: training the whole ``RNNT`` module is out of scope."""
+    It differentiates the joint network's output layer and its two projected inputs; ``RNNT.loss`` chains it with the
+    predictor's and the projections' backward.  The encoder modules have no backward in this project."""
     if reduction not in _REDUCTIONS:
         raise ValueError(f"{reduction} is not a valid value for reduction")
     args, shape = _score_inputs(enc_p, pred_p, w_out, b_out, in_lens, targets, target_lens, blank)

@@ -1,0 +1,240 @@
+"""Training pieces for the transducer's prediction network -- this repository's OWN specification (the comment on
+``ms_lstm_recompute`` in include/ms_hotpath.h; tests/lstm_backward_ref.py restates it in numpy).
+
+``lstm_train(rnn, x, lens, hx)`` is ``RNN.forward`` on a unidirectional LSTM stack as an autograd node.  The forward is the
+existing ``run_layers`` called one layer at a time with the stack's own ``PackedLayer`` objects, so every layer's output
+exists as a tensor (a padded width is sliced by ``run_layers`` as always).  The forward kernels save no gates: the backward
+rebuilds them per layer, top down (``ms_lstm_recompute``: two batch GEMMs and a scan), runs the recurrence backwards
+(``ms_lstm_backward_steps``: one launch per step, float32 MFMA) and finishes with three batch GEMMs through
+``ms_linear_forward`` -- dx = dG w_ih, d_w_ih = dG^T x, d_w_hh = dG^T h_prev.  Gradients reach x, every
+``weight_ih_l*`` / ``weight_hh_l*`` / ``bias_*_l*`` and hx.
+
+``linear_train`` and ``embedding_train`` are the two small nodes around it: a linear layer whose forward and backward
+products all run through ``ms_linear_forward`` (db is a ones-row product), and the embedding look-up whose backward is
+``ms_embedding_backward``.
+
+Out of scope, and refused with ValueError before a device is needed: GRU and tanh cells, ``bidirectional=True``,
+inter-layer dropout in training mode.  There is no backward for the convolutions or the encoder's stacks, no
+single-launch (persistent) backward recurrence and no mixed-precision gradient.
+"""
+from typing import Optional, Tuple
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from myrtlespeech_amd import _lib
+from myrtlespeech_amd.model.rnn import RNN, RNNType, run_layers
+
+
+def gemm_nt(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a [M, K] . b [N, K]^T (+ bias [N]) -> [M, N] through ``ms_linear_forward`` (exact float32 MFMA, one k-ordered chain)."""
+    a, b = a.contiguous(), b.contiguous()
+    m, k = a.shape
+    n = b.shape[0]
+    y = torch.empty((m, n), dtype=torch.float32, device="cuda")
+    _lib.check(_lib.load().ms_linear_forward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(bias), _lib.ptr(y), m, k, n, _lib.ACT_NONE, 0.0,
+                                             0.0, _lib.stream_ptr()), "ms_linear_forward")
+    return y
+
+
+def _like(g: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
+    return g.to(device=ref.device, dtype=ref.dtype).reshape(ref.shape)
+
+
+class _LinearFunction(torch.autograd.Function):
+    """y = x w^T + b; backward: dx = dy w, dw = dy^T x, db = 1^T dy, each a product of ``ms_linear_forward``."""
+
+    @staticmethod
+    def forward(ctx, x2d, weight, bias):
+        x = _lib.f32c(x2d.detach())
+        w = _lib.f32c(weight.detach())
+        b = None if bias is None else _lib.f32c(bias.detach())
+        ctx.save_for_backward(x, w)
+        ctx.like = (x2d, weight, bias)
+        return gemm_nt(x, w, b)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        x_like, w_like, b_like = ctx.like
+        dy = _lib.f32c(dy)
+        need = ctx.needs_input_grad
+        dx = _like(gemm_nt(dy, w.t()), x_like) if need[0] else None
+        dy_t = dy.t().contiguous() if (need[1] or (b_like is not None and need[2])) else None
+        dw = _like(gemm_nt(dy_t, x.t()), w_like) if need[1] else None
+        db = None
+        if b_like is not None and need[2]:
+            ones = torch.ones((1, dy.shape[0]), dtype=torch.float32, device="cuda")
+            db = _like(gemm_nt(ones, dy_t), b_like)
+        return dx, dw, db
+
+
+def linear_train(x2d: torch.Tensor, lin: torch.nn.Linear) -> torch.Tensor:
+    """``lin(x2d)`` for x2d [M, K] as an autograd node on the device."""
+    return _LinearFunction.apply(x2d, lin.weight, lin.bias)
+
+
+class _EmbeddingFunction(torch.autograd.Function):
+    """out[r] = table[clamp(idx[r])] (``ms_embedding_forward``); backward ``ms_embedding_backward``."""
+
+    @staticmethod
+    def forward(ctx, table, idx):
+        w = _lib.f32c(table.detach())
+        rows = idx.numel()
+        out = torch.empty(tuple(idx.shape) + (w.shape[1],), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.load().ms_embedding_forward(_lib.ptr(w), _lib.ptr(idx), _lib.ptr(out), rows, w.shape[1], w.shape[0],
+                                                    _lib.stream_ptr()), "ms_embedding_forward")
+        ctx.save_for_backward(idx)
+        ctx.like = table
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        (idx,) = ctx.saved_tensors
+        table = ctx.like
+        v1, d = table.shape
+        d_out = _lib.f32c(d_out)
+        d_table = torch.empty((v1, d), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.load().ms_embedding_backward(_lib.ptr(d_out), _lib.ptr(idx), _lib.ptr(d_table), idx.numel(), d, v1,
+                                                     _lib.stream_ptr()), "ms_embedding_backward")
+        return _like(d_table, table), None
+
+
+def embedding_train(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """idx [...] int32 on the device -> [..., D], differentiable in ``table``."""
+    return _EmbeddingFunction.apply(table, idx)
+
+
+class _LSTMStackFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, *flat):
+        nl = rnn.rnn.num_layers
+        hidden = rnn.rnn.hidden_size
+        params = rnn._layer_params()
+        xin = _lib.f32c(x.detach())
+        h0d = _lib.f32c(h0.detach()) if has_hx else None
+        c0d = _lib.f32c(c0.detach()) if has_hx else None
+        layer_in, hns, cns = [xin], [], []
+        for layer in range(nl):
+            out, hn, cn = run_layers(_lib.CELL_LSTM, layer_in[-1], lens_dev, max_len, [params[layer]], [rnn._packed[layer]], hidden,
+                                     None if h0d is None else h0d[layer:layer + 1], None if c0d is None else c0d[layer:layer + 1],
+                                     rnn._workspace, rnn.check_status, ragged=ragged)
+            layer_in.append(out.contiguous())
+            hns.append(hn)
+            cns.append(cn)
+        weights = [None if p is None else _lib.f32c(p.detach()) for p in flat]
+        ctx.save_for_backward(*layer_in, *([h0d, c0d] if has_hx else []), *[w for w in weights if w is not None])
+        ctx.meta = dict(nl=nl, hidden=hidden, lens_dev=lens_dev, max_len=max_len, has_hx=has_hx,
+                        has_w=[w is not None for w in weights], like=(x, h0, c0) + tuple(flat))
+        return layer_in[-1], torch.cat(hns, 0), torch.cat(cns, 0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out, d_hn, d_cn):
+        m = ctx.meta
+        nl, hidden, lens_dev, max_len = m["nl"], m["hidden"], m["lens_dev"], m["max_len"]
+        saved = list(ctx.saved_tensors)
+        layer_in = saved[:nl + 1]
+        pos = nl + 1
+        h0 = c0 = None
+        if m["has_hx"]:
+            h0, c0 = saved[pos], saved[pos + 1]
+            pos += 2
+        weights = []
+        for has in m["has_w"]:
+            weights.append(saved[pos] if has else None)
+            pos += has
+        lib = _lib.load()
+        t, n, _ = layer_in[0].shape
+        rows = t * n
+        nbytes = lib.ms_lstm_recompute_workspace_bytes(t, n, hidden)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")                      # transient
+        gates = torch.empty((t, n, 4 * hidden), dtype=torch.float32, device="cuda")
+        cells = torch.empty((t, n, hidden), dtype=torch.float32, device="cuda")
+        live = (torch.arange(t, device="cuda")[:, None] < lens_dev[None, :]).unsqueeze(-1)     # [T, N, 1]: the rows that exist
+        d_top = _lib.f32c(d_out)
+        d_hn = None if d_hn is None else _lib.f32c(d_hn)
+        d_cn = None if d_cn is None else _lib.f32c(d_cn)
+        d_h0s, d_c0s = [None] * nl, [None] * nl
+        w_grads = [None] * (4 * nl)
+        for layer in range(nl - 1, -1, -1):
+            w_ih, w_hh, b_ih, b_hh = weights[4 * layer:4 * layer + 4]
+            xl, hl = layer_in[layer], layer_in[layer + 1]
+            in_size = xl.shape[2]
+            h0l = None if h0 is None else h0[layer].contiguous()
+            c0l = None if c0 is None else c0[layer].contiguous()
+            _lib.check(lib.ms_lstm_recompute(_lib.ptr(xl), _lib.ptr(hl), _lib.ptr(h0l), _lib.ptr(c0l), _lib.ptr(lens_dev),
+                                             _lib.ptr(w_ih), _lib.ptr(w_hh), _lib.ptr(b_ih), _lib.ptr(b_hh), _lib.ptr(gates),
+                                             _lib.ptr(cells), t, n, in_size, hidden, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "ms_lstm_recompute")
+            d_g = torch.empty((t, n, 4 * hidden), dtype=torch.float32, device="cuda")
+            d_h0 = torch.empty((n, hidden), dtype=torch.float32, device="cuda")
+            d_c0 = torch.empty((n, hidden), dtype=torch.float32, device="cuda")
+            d_b = torch.empty(4 * hidden, dtype=torch.float32, device="cuda")
+            _lib.check(lib.ms_lstm_backward_steps(_lib.ptr(gates), _lib.ptr(cells), _lib.ptr(c0l), _lib.ptr(w_hh), _lib.ptr(d_top),
+                                                  _lib.ptr(None if d_hn is None else d_hn[layer].contiguous()),
+                                                  _lib.ptr(None if d_cn is None else d_cn[layer].contiguous()),
+                                                  _lib.ptr(lens_dev), max_len, _lib.ptr(d_g), _lib.ptr(d_h0), _lib.ptr(d_c0),
+                                                  _lib.ptr(d_b), t, n, hidden, _lib.stream_ptr()), "ms_lstm_backward_steps")
+            g2 = d_g.reshape(rows, 4 * hidden)
+            g2_t = g2.t().contiguous()
+            h_prev = torch.cat([(torch.zeros((1, n, hidden), dtype=torch.float32, device="cuda") if h0l is None else h0l[None]),
+                                hl[:-1]], 0)
+            # (dG is exactly 0 in the rows past a length and the layers' outputs are 0 there; what the CALLER left in those
+            # rows of x may be anything, a NaN included, and must not reach the sum)
+            x_rows = torch.where(live, xl, torch.zeros((), dtype=torch.float32, device="cuda")) if layer == 0 else xl
+            w_grads[4 * layer] = gemm_nt(g2_t, x_rows.reshape(rows, in_size).t())
+            w_grads[4 * layer + 1] = gemm_nt(g2_t, h_prev.reshape(rows, hidden).t())
+            w_grads[4 * layer + 2] = d_b if b_ih is not None else None
+            w_grads[4 * layer + 3] = d_b if b_hh is not None else None
+            d_h0s[layer], d_c0s[layer] = d_h0, d_c0
+            if layer > 0 or ctx.needs_input_grad[5]:
+                d_top = gemm_nt(g2, w_ih.t()).reshape(t, n, in_size)
+        x_like, h_like, c_like = m["like"][:3]
+        dx = _like(d_top, x_like) if ctx.needs_input_grad[5] else None
+        dh0 = _like(torch.stack(d_h0s, 0), h_like) if (m["has_hx"] and ctx.needs_input_grad[6]) else None
+        dc0 = _like(torch.stack(d_c0s, 0), c_like) if (m["has_hx"] and ctx.needs_input_grad[7]) else None
+        flat = []
+        for k, (g, like) in enumerate(zip(w_grads, m["like"][3:])):
+            flat.append(None if (g is None or like is None or not ctx.needs_input_grad[8 + k]) else _like(g, like))
+        return (None, None, None, None, None, dx, dh0, dc0, *flat)
+
+
+def lstm_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+               ) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+    """x [T, N, In] time-major, lens [N] sorted descending, hx = (h0, c0) [num_layers, N, H] or None (zeros) ->
+    ``(out [T, N, H], (h_n, c_n))`` with ``RNN.forward``'s values (rows past a length are 0, the states are those at
+    ``lens[n] - 1``), differentiable in x, hx and every parameter of the stack.  ``RNN.forward`` itself is untouched."""
+    if not isinstance(rnn, RNN) or rnn.rnn_type != RNNType.LSTM:
+        raise ValueError("lstm_train serves LSTM stacks only (GRU and tanh cells have no backward in this project)")
+    if rnn.bidirectional:
+        raise ValueError("lstm_train does not serve bidirectional=True (no backward for the reverse direction)")
+    if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
+        raise ValueError("lstm_train does not serve inter-layer dropout in training mode")
+    if rnn.batch_first:
+        raise ValueError("lstm_train takes time-major input (batch_first=False)")
+    if x.dim() != 3 or x.shape[2] != rnn.rnn.input_size or min(x.shape) <= 0:
+        raise ValueError(f"x must be [T, N, In] with In = {rnn.rnn.input_size}, got {tuple(x.shape)}")
+    t, n, _ = x.shape
+    if not isinstance(lens, torch.Tensor) or lens.is_floating_point():
+        raise ValueError("lens must be an integer tensor")
+    lens_cpu = _lib.host_lens(lens).reshape(-1)
+    if lens_cpu.numel() != n:
+        raise ValueError(f"expected {n} lengths, got {lens_cpu.numel()}")
+    if bool((lens_cpu[:-1] < lens_cpu[1:]).any()):
+        raise ValueError("lens must be sorted in decreasing order")
+    if int(lens_cpu.min()) < 1 or int(lens_cpu.max()) > t:
+        raise ValueError(f"lengths must be in [1, {t}]")
+    nl, hidden = rnn.rnn.num_layers, rnn.rnn.hidden_size
+    if hx is not None:
+        if len(hx) != 2 or any(tuple(s.shape) != (nl, n, hidden) for s in hx):
+            raise ValueError(f"hx must be (h0, c0), each [{nl}, {n}, {hidden}]")
+    _lib.require_gpu()
+    max_len = int(lens_cpu[0])
+    flat = [p for layer in rnn._layer_params() for p in layer[0]]
+    h0, c0 = hx if hx is not None else (None, None)
+    out, hn, cn = _LSTMStackFunction.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None,
+                                           x, h0, c0, *flat)
+    return out, (hn, cn)

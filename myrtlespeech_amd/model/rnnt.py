@@ -47,21 +47,29 @@ class RNNTPredictor(torch.nn.Module):
         (out, _), new_state = self.rnn((emb, torch.ones(r, dtype=torch.int64)), state)
         return out[0], new_state
 
-    def forward_targets(self, targets: torch.Tensor, target_lens: torch.Tensor) -> torch.Tensor:
+    def forward_targets(self, targets: torch.Tensor, target_lens: torch.Tensor, differentiable: bool = False) -> torch.Tensor:
         """targets [N, U] padded labels -> pred [U + 1, N, hidden]: row u is the prediction after ``y_n[:u]`` (u = 0: after
         the start symbol), for GIVEN transcripts.  ONE embedding look-up over ``[blank, y_0 .. y_{U-1}]`` of the whole batch
         (time-major rows) and ONE call of the recurrent stack on the [U + 1, N, D] sequence from a zero state, where ``step``
         (kept for the decoders) would take U + 1 rounds.  The predictor is causal, so what the padding of ``targets`` holds
-        (the look-up clamps it) only reaches rows u > target_lens[n]; ``target_lens`` is checked against the batch only."""
+        (the look-up clamps it) only reaches rows u > target_lens[n]; ``target_lens`` is checked against the batch only.
+        Detached by default.  ``differentiable=True``: the same look-up and the same stack as autograd nodes
+        (``model.rnn_autograd``: ``embedding_train``, ``lstm_train``), so a gradient of ``pred`` reaches the embedding table
+        and every LSTM parameter."""
         if targets.dim() != 2 or targets.is_floating_point():
             raise ValueError(f"targets must be an integer tensor [N, U], got {tuple(targets.shape)} {targets.dtype}")
         n, u_max = targets.shape
         if n <= 0 or target_lens.numel() != n:
             raise ValueError(f"target lengths of batch {target_lens.numel()} != targets batch {n}")
         _lib.require_gpu()
-        w = _lib.f32c(self.embedding.weight.detach())
         y = targets.detach().to(device="cuda", dtype=torch.int32)
         idx = torch.cat([torch.full((1, n), self.blank, dtype=torch.int32, device="cuda"), y.t()], 0).contiguous()
+        if differentiable:
+            from myrtlespeech_amd.model.rnn_autograd import embedding_train, lstm_train
+            emb = embedding_train(self.embedding.weight, idx)                   # [U + 1, N, D]
+            out, _ = lstm_train(self.rnn, emb, torch.full((n,), u_max + 1, dtype=torch.int64))
+            return out
+        w = _lib.f32c(self.embedding.weight.detach())
         rows = (u_max + 1) * n
         emb = torch.empty((u_max + 1, n, w.shape[1]), dtype=torch.float32, device="cuda")
         _lib.check(_lib.load().ms_embedding_forward(_lib.ptr(w), _lib.ptr(idx), _lib.ptr(emb), rows, w.shape[1], w.shape[0],
@@ -91,10 +99,29 @@ class RNNTJoint(torch.nn.Module):
                                          _lib.ACT_NONE, 0.0, 0.0, _lib.stream_ptr()), "ms_linear_forward")
         return y
 
-    def project_encoder(self, enc: torch.Tensor) -> torch.Tensor:
-        """enc [T, N, E] -> [T*N, J] (done once per batch)."""
+    def project_encoder(self, enc: torch.Tensor, differentiable: bool = False) -> torch.Tensor:
+        """enc [T, N, E] -> [T*N, J] (done once per batch).  ``differentiable=True``: as an autograd node
+        (``model.rnn_autograd.linear_train``) whose gradients reach ``enc_proj`` and ``enc``."""
+        if differentiable:
+            if enc.dim() != 3 or enc.shape[2] != self.enc_proj.in_features:
+                raise ValueError(f"enc must be [T, N, {self.enc_proj.in_features}], got {tuple(enc.shape)}")
+            _lib.require_gpu()
+            from myrtlespeech_amd.model.rnn_autograd import linear_train
+            return linear_train(enc.reshape(enc.shape[0] * enc.shape[1], enc.shape[2]), self.enc_proj)
         t, n, e = enc.shape
         return self._linear(_lib.f32c(enc).reshape(t * n, e), self.enc_proj)
+
+    def project_predictor(self, pred: torch.Tensor, differentiable: bool = False) -> torch.Tensor:
+        """pred [U + 1, N, H] (``RNNTPredictor.forward_targets``) -> [(U + 1)*N, J].  ``differentiable=True``: as an autograd
+        node whose gradients reach ``pred_proj`` and ``pred``."""
+        if pred.dim() != 3 or pred.shape[2] != self.pred_proj.in_features:
+            raise ValueError(f"pred must be [U + 1, N, {self.pred_proj.in_features}], got {tuple(pred.shape)}")
+        _lib.require_gpu()
+        rows = pred.shape[0] * pred.shape[1]
+        if differentiable:
+            from myrtlespeech_amd.model.rnn_autograd import linear_train
+            return linear_train(pred.reshape(rows, pred.shape[2]), self.pred_proj)
+        return self._linear(_lib.f32c(pred).reshape(rows, -1), self.pred_proj)
 
     def logprobs(self, enc_p: torch.Tensor, enc_rows: torch.Tensor, pred_out: torch.Tensor) -> torch.Tensor:
         """log P(symbol | frame, prefix) for R hypothesis rows: enc_rows [R] indexes rows of ``enc_p``."""
@@ -178,6 +205,33 @@ class RNNT(torch.nn.Module):
             pred_p = self.joint._linear(_lib.f32c(pred).reshape(u1 * n, -1), self.joint.pred_proj)   # [U1*N, J], row u*N + n
             return rnnt_score(enc_p.reshape(t, n, -1), pred_p.reshape(u1, n, -1), w.detach(), None if b is None else b.detach(),
                               lens, targets, target_lens, blank)
+
+    def loss(self, enc: torch.Tensor, lens: torch.Tensor, targets: torch.Tensor, target_lens: torch.Tensor,
+             reduction: str = "mean") -> torch.Tensor:
+        """The transducer loss of GIVEN transcripts as a differentiable call, WITHOUT the logit lattice: the plumbing of
+        ``transcript_nll`` with every stage an autograd node -- ``joint.project_encoder``, ``predictor.forward_targets`` and
+        ``joint.project_predictor`` with ``differentiable=True``, then ``loss.rnnt_loss.rnnt_joint_loss`` (its reductions:
+        ``none`` nll [N], ``sum``, ``mean`` = the sum divided by N).  enc [T, N, E] encoder frames, targets [N, U] padded
+        labels.  Gradients reach ``predictor.embedding.weight``, every parameter of the predictor's LSTM, ``joint.enc_proj``,
+        ``joint.pred_proj`` and ``joint.out`` -- and ``enc`` itself when it requires grad.  That is where the chain ends: the
+        encoder modules (convolutions, bidirectional stacks, GRU) still have no backward in this project, so ``enc`` must be
+        a leaf or come from torch ops; this trains or adapts the prediction network and the joint on a frozen encoder."""
+        from myrtlespeech_amd.loss.rnnt_loss import _REDUCTIONS, check_score_shapes, rnnt_joint_loss
+        if reduction not in _REDUCTIONS:
+            raise ValueError(f"{reduction} is not a valid value for reduction")
+        if enc.dim() != 3 or targets.dim() != 2 or targets.shape[0] != enc.shape[1]:
+            raise ValueError(f"enc must be [T, N, E] and targets [N, U], got {tuple(enc.shape)} and {tuple(targets.shape)}")
+        t, n, _ = enc.shape
+        u1 = targets.shape[1] + 1
+        w, b = self.joint.out.weight, self.joint.out.bias
+        blank = self.predictor.blank
+        check_score_shapes(t, n, u1, w.shape[1], w.shape[0], lens, targets, target_lens, blank)
+        _lib.require_gpu()
+        enc_p = self.joint.project_encoder(enc, differentiable=True)                        # [T*N, J], row t*N + n
+        pred = self.predictor.forward_targets(targets, target_lens, differentiable=True)     # [U1, N, H]
+        pred_p = self.joint.project_predictor(pred, differentiable=True)                    # [U1*N, J], row u*N + n
+        return rnnt_joint_loss(enc_p.reshape(t, n, -1), pred_p.reshape(u1, n, -1), w, b, lens, targets, target_lens, blank,
+                               reduction)
 
     def align(self, enc: torch.Tensor, lens: torch.Tensor, targets: torch.Tensor, target_lens: torch.Tensor):
         """Forced alignment of GIVEN transcripts, WITHOUT the logit lattice: enc [T, N, E] encoder frames, targets [N, U]
