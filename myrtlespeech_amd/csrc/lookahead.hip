@@ -45,6 +45,41 @@ __global__ __launch_bounds__(256) void lookahead_tcontig_kernel(const float* __r
 // the loads and no outputs computed for nothing); the per-output order of the products is the same for every TT.
 constexpr int LA_TT = 32, LA_KC = 16;
 
+// One chunk of LA_KC taps starting at tap k0.  TAIL = the last, partial chunk of a context that is no multiple of LA_KC: its
+// taps k0 + k >= ctx do not exist, and their products are SKIPPED (a condition that is uniform over the launch), not
+// multiplied by a zero weight -- 0 x Inf is NaN, and a tap that the context does not have would carry an Inf or NaN of
+// frame t back to outputs before t - (ctx - 1), which neither the reference nor the time-contiguous kernel does.
+template <int TT, bool TAIL>
+__device__ __forceinline__ void lookahead_chunk(const float* __restrict__ xr, const float* __restrict__ wr, float (&acc)[TT],
+                                                int t0, int k0, int T, int ctx, long xs_t) {
+  float wk[LA_KC], xv[TT + LA_KC - 1];
+#pragma unroll
+  for (int j = 0; j < TT + LA_KC - 1; ++j) xv[j] = xr[(long)min(t0 + k0 + j, T - 1) * xs_t];
+#pragma unroll
+  for (int k = 0; k < LA_KC; ++k) wk[k] = wr[TAIL ? min(k0 + k, ctx - 1) : k0 + k];
+#pragma unroll
+  for (int j = 0; j < TT + LA_KC - 1; ++j) xv[j] = (t0 + k0 + j < T) ? xv[j] : 0.f;
+  if (!TAIL) {
+    // (round 6) output-major: two loops of constant trip count, every index static.  The input-major form (for j: for i:
+    // k = j - i, guarded) left hipcc's unroller with a 47 x 32 body at TT = 32 that it did not flatten: xv[] was indexed at
+    // run time and lived in scratch memory (192 bytes per lane).  Per output the products still arrive in tap order.
+#pragma unroll
+    for (int i = 0; i < TT; ++i) {
+#pragma unroll
+      for (int k = 0; k < LA_KC; ++k) acc[i] += wk[k] * xv[i + k];
+    }
+  } else {
+    // tap-major, so that the guard is one uniform branch per tap; per output the products arrive in tap order all the same
+#pragma unroll
+    for (int k = 0; k < LA_KC; ++k) {
+      if (k0 + k < ctx) {
+#pragma unroll
+        for (int i = 0; i < TT; ++i) acc[i] += wk[k] * xv[i + k];
+      }
+    }
+  }
+}
+
 template <int TT>
 __global__ __launch_bounds__(256) void lookahead_strided_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                 float* __restrict__ y, int F, int T, int To, int ctx,
@@ -57,25 +92,9 @@ __global__ __launch_bounds__(256) void lookahead_strided_kernel(const float* __r
   float acc[TT];
 #pragma unroll
   for (int i = 0; i < TT; ++i) acc[i] = 0.f;
-  for (int k0 = 0; k0 < ctx; k0 += LA_KC) {
-    float wk[LA_KC], xv[TT + LA_KC - 1];
-#pragma unroll
-    for (int j = 0; j < TT + LA_KC - 1; ++j) xv[j] = xr[(long)min(t0 + k0 + j, T - 1) * xs_t];
-#pragma unroll
-    for (int k = 0; k < LA_KC; ++k) wk[k] = wr[min(k0 + k, ctx - 1)];
-#pragma unroll
-    for (int k = 0; k < LA_KC; ++k) wk[k] = (k0 + k < ctx) ? wk[k] : 0.f;
-#pragma unroll
-    for (int j = 0; j < TT + LA_KC - 1; ++j) xv[j] = (t0 + k0 + j < T) ? xv[j] : 0.f;
-    // (round 6) output-major: two loops of constant trip count, every index static.  The input-major form (for j: for i:
-    // k = j - i, guarded) left hipcc's unroller with a 47 x 32 body at TT = 32 that it did not flatten: xv[] was indexed at
-    // run time and lived in scratch memory (192 bytes per lane).  Per output the products still arrive in tap order.
-#pragma unroll
-    for (int i = 0; i < TT; ++i) {
-#pragma unroll
-      for (int k = 0; k < LA_KC; ++k) acc[i] += wk[k] * xv[i + k];
-    }
-  }
+  int k0 = 0;
+  for (; k0 + LA_KC <= ctx; k0 += LA_KC) lookahead_chunk<TT, false>(xr, wr, acc, t0, k0, T, ctx, xs_t);
+  if (k0 < ctx) lookahead_chunk<TT, true>(xr, wr, acc, t0, k0, T, ctx, xs_t);
 #pragma unroll
   for (int i = 0; i < TT; ++i) {
     const int t = t0 + i;
