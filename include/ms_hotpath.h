@@ -116,7 +116,10 @@ int ms_maskconv_cl_forward(const float* x, const int32_t* lens, const void* pack
  * multiple of 16), the KT time taps stay taps.  x is [N, 1, Fin, Tin]; the workspace holds its feature-contiguous bf16
  * hi / lo planes [N, Tin, FP] with the SAME feature padding materialised; mask (t >= lens[n]) and time padding are load
  * predicates; bias + clamp in the epilogue; y is [N, Cout, Fout, Tout] float32.  MS_ERR_UNSUPPORTED when the staged
- * rows do not fit LDS (the caller then uses ms_maskconv_forward). */
+ * rows do not fit LDS (the caller then uses ms_maskconv_forward).  The window's KF rows are padded to whole 16-row k-steps
+ * with zero filters, which multiply the input rows under the window: in the two-plane modes the planes therefore hold the
+ * input clamped to the finite range of their format (f16x3: +-65504, as everywhere; bf16x3: +-3.39e38), so that a non-finite
+ * input value reaches only the outputs whose window holds it (the one-plane fp16 mode does not clamp). */
 size_t ms_maskconv_fwin_packed_bytes(int Cout, int KF, int KT);
 int ms_maskconv_fwin_pack(const float* w, void* packed, int Cout, int KF, int KT, void* stream);
 size_t ms_maskconv_fwin_workspace_bytes(int N, int Tin, int KF, int SF, int Fout);
@@ -154,7 +157,8 @@ int ms_conv_set_variant(int variant);
 /* MaskConv1d with many input channels as im2col + split-bf16 GEMM (model/cnn.py:295-333, the conv1d flavour of the DS2
  * builder): x [N, Cin, Tin] -> y [N, Cout, Tout]; frames t >= lens[n] read as zero (cnn.py:280-293), pad_l zero
  * frames on the left (cnn.py:252-278); packed = ms_maskconv1d_gemm_pack of weight [Cout, Cin, KT]; bias may be NULL;
- * groups = 1.  Products carry the split-bf16 error (~2^-17 relative, like ms_linear_split_forward). */
+ * groups = 1; MS_ERR_WORKSPACE for a workspace below ms_maskconv1d_gemm_workspace_bytes.  Products carry the split-bf16 error
+ * (~2^-17 relative, like ms_linear_split_forward). */
 size_t ms_maskconv1d_gemm_packed_bytes(int Cout, int Cin, int KT);
 int ms_maskconv1d_gemm_pack(const float* w, void* packed, int Cout, int Cin, int KT, void* stream);
 size_t ms_maskconv1d_gemm_workspace_bytes(int N, int Cin, int Tout, int Cout, int KT);

@@ -7,7 +7,8 @@
 //
 // Decomposition: one workgroup (4 waves) owns 32 output channels x 128 output frames of
 // one (n, f_out) row; wave w owns frames [32w, 32w+32).  The reduction axis is walked as
-// rows r = (cin, kf) x kernel-time taps kt (padded to an even count KT2 with zero taps).
+// rows r = (cin, kf) x kernel-time taps kt (padded to an even count KT2 with zero taps, which
+// meet a zero operand, never the input).
 // Per chunk of RC rows the workgroup stages
 //   Wl[r][kt][32 cout]      (contiguous copy out of the pre-packed filter bank)
 //   Pl[r][p]                (the input row f_in = f_out*SF - pad_f + kf*DF, frames
@@ -74,9 +75,15 @@ __global__ __launch_bounds__(256) void maskconv_kernel(const float* __restrict__
   const int tin0 = t0 * p.ST - p.pad_t;
   const int fin0 = fo * p.SF - p.pad_f;
   const int bcol = (wave * 32 + l31) * p.ST + half * p.DT;
+  // The last pair of taps is read by offsets of its own: with an odd KT the second tap of that pair is the bank's zero tap,
+  // and its half of the wave reads the zero in the row's spare column PW, not the frame one tap past the window (0 x Inf =
+  // NaN in an output that never reads that frame).
+  const int last_pair = p.KT2 / 2 - 1;
+  const int last_a = (2 * last_pair + half) * CO_T + l31;
+  const int last_b = ((p.KT & 1) && half) ? p.PW : bcol + 2 * last_pair * p.DT;
 
   for (int r0 = 0; r0 < p.R; r0 += RC_MAX) {
-    const int rc = min(RC_MAX, p.R - r0);
+    const int rc = __builtin_amdgcn_readfirstlane(min(RC_MAX, p.R - r0));   // (scalar loop control)
     // stage the filter chunk: contiguous rc*KT2*32 floats
     {
       const int nf = rc * p.KT2 * CO_T;  // multiple of 64 (KT2 even)
@@ -97,16 +104,20 @@ __global__ __launch_bounds__(256) void maskconv_kernel(const float* __restrict__
         if (frow && tin >= 0 && tin < len) v = xr[tin];
         Pl[rr * p.PWS + q] = v;
       }
+      if (lane == 0) Pl[rr * p.PWS + p.PW] = 0.f;
     }
     __syncthreads();
     for (int rr = 0; rr < rc; ++rr) {
       const float* wrow = Wl + rr * p.KT2 * CO_T + half * CO_T + l31;
       const float* prow = Pl + rr * p.PWS + bcol;
-      for (int m = 0; m < p.KT2 / 2; ++m) {
+      const float a_last = Wl[rr * p.KT2 * CO_T + last_a];   // (requested first: they arrive under the other pairs' MFMAs)
+      const float b_last = Pl[rr * p.PWS + last_b];
+      for (int m = 0; m < last_pair; ++m) {
         const float a = wrow[2 * m * CO_T];
         const float b = prow[2 * m * p.DT];
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
       }
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_last, b_last, acc, 0, 0, 0);
     }
     __syncthreads();
   }

@@ -130,7 +130,10 @@ extern "C" int ms_maskconv1d_gemm_forward(const float* x, const int32_t* lens, c
   MS_REQUIRE(N > 0 && Cin > 0 && Tin > 0 && Cout > 0 && Tout > 0 && KT > 0 && ST > 0 && DT > 0 && pad_l >= 0, "bad shape");
   MS_REQUIRE(act == MS_ACT_NONE || act == MS_ACT_CLAMP, "bad act");
   MS_REQUIRE(N <= 65535 && Tout <= 65535 * 32 && (long long)N * Tout <= 2147483647LL, "N / Tout exceed grid limits");
-  MS_REQUIRE(workspace_bytes >= ms_maskconv1d_gemm_workspace_bytes(N, Cin, Tout, Cout, KT), "workspace too small");
+  if (workspace_bytes < ms_maskconv1d_gemm_workspace_bytes(N, Cin, Tout, Cout, KT)) {
+    ms::set_error("ms_maskconv1d_gemm_forward: workspace too small");
+    return MS_ERR_WORKSPACE;
+  }
   hipStream_t stream = (hipStream_t)stream_;
   const int K = Cin * KT, Kp = padded_k(Cin, KT);
   const size_t rows = (size_t)N * Tout;

@@ -619,6 +619,8 @@ __global__ void nchw_to_cl_split_kernel(const float* __restrict__ x, unsigned sh
   }
 }
 
+constexpr float BF16_MAX = 3.3895313892515355e38f;   // 0x7F7F0000
+
 // single-channel input x [N][Fin][T] f32 -> bf16 hi / lo planes [N][T][FP], element j = feature j - pad (zeros outside)
 __global__ void ft_to_tf_split_kernel(const float* __restrict__ x, unsigned short* __restrict__ hi,
                                       unsigned short* __restrict__ lo, int Fin, int T, int FP, int pad, int prec) {
@@ -634,7 +636,11 @@ __global__ void ft_to_tf_split_kernel(const float* __restrict__ x, unsigned shor
   for (int i = ty; i < 32; i += 8) {
     const int t = t0 + i, j = j0 + tx;
     if (t < T && j < FP) {
-      const float v = tile[tx][i];
+      float v = tile[tx][i];
+      // The rows under a window (its KF rows are padded to whole 16-row k-steps) meet the zero filters of
+      // conv_fwin_pack_kernel, and 0 x Inf is NaN in an output that does not read that row: bf16 planes take their operands
+      // clamped to the format's finite range, as plane_bits<true> clamps those of the fp16 planes.
+      if (prec == ms::PREC_BF16X3) v = __builtin_amdgcn_fmed3f(v, -BF16_MAX, BF16_MAX);
       const size_t o = ((size_t)n * T + t) * FP + j;
       unsigned h, l;
       split_by_prec(v, prec, h, l);
