@@ -194,9 +194,21 @@ size_t ms_linear_splitk_workspace_bytes(int M, int K, int N, int flags);
 int ms_linear_splitk_forward(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int act,
                              float act_lo, float act_hi, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Same contract as ms_linear_forward for K % 32 == 0, computed with float32 operands split
- * into bf16 hi + lo (x.w ~= x_hi.w_hi + x_lo.w_hi + x_hi.w_lo, f32 accumulate; relative error
- * ~2^-17 per product).  The workspace holds the four bf16 planes. */
+/* Same contract as ms_linear_forward for K % 32 == 0, computed with float32 operands split into 16-bit planes in the
+ * process's MS_PRECISION mode, hi = rn(v), lo = rn(v - hi):
+ *   "f16x3" (default)  fp16 hi + lo, 22 significant bits of every operand;
+ *   "bf16x3"           bf16 hi + lo, 16 significant bits;
+ *   "fp16"             one fp16 plane, 11 significant bits, one product;
+ * y = act(sum_k (x_hi.w_hi + x_lo.w_hi + x_hi.w_lo) + bias) with float32 products and sums (x_lo.w_lo is left out; "fp16":
+ * sum_k x_hi.w_hi).  The fp16 formats hold +-65504: a finite operand is clamped to that range before each rounding, so values
+ * up to 2 x 65504 still come out through the lo plane and larger ones read as +-131008 ("fp16": +-65504); bf16 planes have
+ * float32's range.  Non-finite values are kept: a NaN in x[m, k] makes row m of y NaN, a NaN in w[n, k] column n, in every
+ * mode and through MS_ACT_CLAMP (which is torch.nn.Hardtanh: NaN stays NaN, +-Inf becomes a bound); a +-Inf operand makes
+ * its row / column non-finite before the activation (NaN in the two-plane modes, whose lo plane is Inf - Inf).  Other rows and
+ * columns are not affected.  This holds for the operands that ms_linear_split_* and the LSTM input projection split; the
+ * convolution entry points (ms_maskconv1d_gemm_forward's im2col planes among them) still saturate a non-finite input to
+ * +-65504 (NaN: -65504) before it reaches these kernels.  The workspace holds the four planes (ms_linear_split_workspace_bytes: M K 4 and N K 4 bytes, each
+ * rounded up to 256); x and w must be 16-byte aligned. */
 size_t ms_linear_split_workspace_bytes(int M, int K, int N);
 int ms_linear_split_forward(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int act,
                             float act_lo, float act_hi, void* workspace, size_t workspace_bytes, void* stream);
@@ -334,7 +346,8 @@ int ms_rnn_status(const void* workspace, void* stream);
 size_t ms_rnn_debug_offset(int cell, int T, int N, int In, int H, int ndir);
 
 /* Tuning switch for same-process A/B runs of the split-operand GEMM (tools/gemm_probe.py): 0 = the shipped choice,
- * 2 = the register-staged kernel (the round-1 kernel; bit-identical results).  Not part of the reference surface. */
+ * 2 = the register-staged kernel (the round-1 kernel), 7 .. 11 = the four-wave 256 x 128 LDS-DMA forms (with bf16 planes they
+ * differ in how a wave issues its DMA pieces); bit-identical results.  Not part of the reference surface. */
 int ms_gemm_set_variant(int variant);
 
 /* Optional launch timing for bench.py's roofline line and its per-stage breakdown (not part of the reference

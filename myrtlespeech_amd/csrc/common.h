@@ -34,6 +34,13 @@ void set_error(const std::string& s);
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// The clamp activation of the GEMM epilogues (Linear + torch.nn.Hardtanh): min(max(v, lo), hi) for every v that is a number,
+// bit for bit, and NaN for a NaN (fminf / fmaxf return their other argument, which would turn a NaN into `lo`).
+__device__ __forceinline__ float act_clamp(float v, float lo, float hi) {
+  const float c = fminf(fmaxf(v, lo), hi);
+  return v != v ? v : c;
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -75,7 +82,9 @@ struct ProfScope {
 // (default since round 6: fp16 hi + lo planes, three fp16 MFMAs).  f16x3 keeps 22 mantissa bits of every operand where
 // bf16x3 keeps 16 -- the MFMA honours fp16 subnormal inputs (tools/micro/mfma_f16_denorm.hip), so a lo plane below 2^-14
 // degrades gradually (absolute step 2^-24) instead of vanishing -- at the same MFMA rate; what it gives up is range: operands
-// are clamped to +-65504 before the split (values up to 2 x 65504 still come out exact to ~2^-11 through the lo plane).
+// are clamped to +-65504 before the split (values up to 2 x 65504 still come out exact to ~2^-11 through the lo plane); the
+// one-plane fp16 mode clamps the same way.  In the planes of a GEMM operand only finite values are clamped: NaN and +-Inf stay
+// what they are (plane_bits_keep).
 // bf16x3's 2^-17 was enough for a default-init network (logits of 0.02) and is NOT for a trained-scale one: 7.7e-3 on
 // logits of 2.8 +- 17 with 4 of 32 greedy transcripts changed (tests/golden/ds2_cfg2_trained_summary.npz).
 enum { PREC_F32 = 0, PREC_BF16X3 = 1, PREC_F16 = 2, PREC_F16X3 = 3 };
@@ -99,9 +108,23 @@ constexpr bool prec_half_planes(int P) { return P == PREC_F16X3 || P == PREC_F16
 typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_ __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8_ __attribute__((ext_vector_type(8)));
+// (a saturating conversion: fmed3 turns +-Inf into +-65504 and a NaN into -65504.  The convolution kernels -- the im2col
+// planes of conv1d_gemm.hip included --, the recurrence's h planes and the transducer kernels convert with it; the operands
+// that ms_linear_split_* splits and the x planes of the LSTM input projection, dense (split_planes_kernel) or packed
+// (rnn.hip: split_planes_packed_kernel), go through plane_bits_keep below)
 template <bool HM>
 __device__ __forceinline__ unsigned plane_bits(float x) {
   if constexpr (HM) return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)__builtin_amdgcn_fmed3f(x, -65504.f, 65504.f));
+  else return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x);
+}
+// The same with non-finite values kept: FINITE values are clamped to +-65504 (the same bits as plane_bits), NaN stays NaN and
+// +-Inf stays +-Inf, so a diverged activation does not come out of a split GEMM finite.  One compare and select more.
+template <bool HM>
+__device__ __forceinline__ unsigned plane_bits_keep(float x) {
+  if constexpr (HM) {
+    const float c = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
+    return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)(__builtin_fabsf(x) < __builtin_inff() ? c : x));
+  }
   else return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x);
 }
 // (for values known to lie in the fp16 range -- a cell's h in [-1, 1]: no clamp on the recurrence's critical path)
@@ -120,6 +143,11 @@ template <bool HM>
 __device__ __forceinline__ void plane_split(float x, unsigned& hi, unsigned& lo) {
   hi = plane_bits<HM>(x);
   lo = plane_bits<HM>(x - plane_val<HM>(hi));
+}
+template <bool HM>
+__device__ __forceinline__ void plane_split_keep(float x, unsigned& hi, unsigned& lo) {   // (x = +-Inf: lo = Inf - Inf = NaN)
+  hi = plane_bits_keep<HM>(x);
+  lo = plane_bits_keep<HM>(x - plane_val<HM>(hi));
 }
 template <bool HM>
 __device__ __forceinline__ void plane_split_bounded(float x, unsigned& hi, unsigned& lo) {

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float* __restric
         const int m = m0 + (wr * TM + i) * 32 + mfma32_row(r, lane);
         if (m < M && n < N) {
           float v = acc[i][j][r] + bv;
-          if (act == MS_ACT_CLAMP) v = fminf(fmaxf(v, lo), hi);
+          if (act == MS_ACT_CLAMP) v = act_clamp(v, lo, hi);
           Y[(size_t)m * N + n] = v;
         }
       }
@@ -205,7 +205,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ parts, float* __r
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < mn; i += (size_t)gridDim.x * blockDim.x) {
     float v = parts[i];
     for (int z = 1; z < ksplit; ++z) v += parts[(size_t)z * mn + i];
-    if (act == MS_ACT_CLAMP) v = fminf(fmaxf(v, lo), hi);
+    if (act == MS_ACT_CLAMP) v = act_clamp(v, lo, hi);
     y[i] = v;
   }
 }

@@ -25,13 +25,11 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ unsigned bf16_hi_bits(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)x); }
 
-__device__ __forceinline__ unsigned f16_bits(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x); }
-
-// fp16 mode: one plane of round-to-nearest fp16 values
+// fp16 mode: one plane of round-to-nearest fp16 values, finite ones clamped to +-65504 like the two-plane format's (common.h)
 __global__ void to_f16_plane_kernel(const float* __restrict__ x, unsigned short* __restrict__ hi, size_t n4) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
     const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-    u32x2 ho = {f16_bits(v[0]) | (f16_bits(v[1]) << 16), f16_bits(v[2]) | (f16_bits(v[3]) << 16)};
+    u32x2 ho = {plane_bits_keep<true>(v[0]) | (plane_bits_keep<true>(v[1]) << 16), plane_bits_keep<true>(v[2]) | (plane_bits_keep<true>(v[3]) << 16)};
     reinterpret_cast<u32x2*>(hi)[i] = ho;
   }
 }
@@ -44,7 +42,7 @@ __global__ void split_planes_kernel(const float* __restrict__ x, unsigned short*
     const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
     unsigned h[4], l[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) plane_split<HM>(v[e], h[e], l[e]);
+    for (int e = 0; e < 4; ++e) plane_split_keep<HM>(v[e], h[e], l[e]);
     u32x2 ho = {h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
     u32x2 lo2 = {l[0] | (l[1] << 16), l[2] | (l[3] << 16)};
     reinterpret_cast<u32x2*>(hi)[i] = ho;
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16x3_kernel(const unsigned s
         const int m = m0 + wave * 64 + i * 32 + mfma32_row(r, lane);
         if (m < M && n < N) {
           float v = acc[i][j][r] + bv;
-          if (act == MS_ACT_CLAMP) v = fminf(fmaxf(v, lo), hi);
+          if (act == MS_ACT_CLAMP) v = act_clamp(v, lo, hi);
           Y[(size_t)m * N + n] = v;
         }
       }
@@ -291,7 +289,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16x3_tile64_kernel(const uns
     const int m = m0 + wm * 32 + mfma32_row(r, lane);
     if (m < M && n < N) {
       float v = acc[r] + bv;
-      if (act == MS_ACT_CLAMP) v = fminf(fmaxf(v, lo), hi);
+      if (act == MS_ACT_CLAMP) v = act_clamp(v, lo, hi);
       Y[(size_t)m * N + n] = v;
     }
   }
@@ -460,7 +458,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_bf16x3_kernel2(const unsigned 
         const int m = m0 + wm * 64 + i * 32 + mfma32_row(r, lane);
         if (m < M && n < N) {
           float v = acc[i][j][r] + bv;
-          if (act == MS_ACT_CLAMP) v = fminf(fmaxf(v, lo), hi);
+          if (act == MS_ACT_CLAMP) v = act_clamp(v, lo, hi);
           Y[(size_t)m * N + n] = v;
         }
       }
@@ -827,7 +825,7 @@ __device__ __forceinline__ void gemm4_body(const unsigned short* __restrict__ Ah
           }
           if (act == MS_ACT_CLAMP && kmode != GEMM_K_FIRST) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fminf(fmaxf(v[e], lo), hi);
+            for (int e = 0; e < 4; ++e) v[e] = act_clamp(v[e], lo, hi);
           }
           *reinterpret_cast<f32x4*>(Y + (size_t)m * N + n) = v;
         } else {
@@ -835,7 +833,7 @@ __device__ __forceinline__ void gemm4_body(const unsigned short* __restrict__ Ah
           for (int e = 0; e < 4; ++e)
             if (n + e < N) {
               float x = v[e] + (bias != nullptr ? bias[n + e] : 0.f);
-              if (act == MS_ACT_CLAMP) x = fminf(fmaxf(x, lo), hi);
+              if (act == MS_ACT_CLAMP) x = act_clamp(x, lo, hi);
               Y[(size_t)m * N + n + e] = x;
             }
         }

@@ -839,7 +839,7 @@ __global__ __launch_bounds__(256) void split_planes_packed_kernel(const float* _
     const float f[4] = {v.x, v.y, v.z, v.w};
     unsigned h[4], l[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ms::plane_split<HM>(f[e], h[e], l[e]);
+    for (int e = 0; e < 4; ++e) ms::plane_split_keep<HM>(f[e], h[e], l[e]);
     *reinterpret_cast<uint2*>(hi + dst + 4 * k) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
     *reinterpret_cast<uint2*>(lo + dst + 4 * k) = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
   }

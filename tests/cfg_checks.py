@@ -340,7 +340,7 @@ def rccl_one_rank() -> None:
 
 
 def gemm_variants_equal() -> None:
-    """The split-operand GEMM's kernels (0 = LDS-DMA 8-wave, 7 / 8 / 10 / 11 = LDS-DMA 4-wave co-tenant forms that differ in how the
+    """The split-operand GEMM's kernels (0 = LDS-DMA 8-wave, 7 / 8 / 9 / 10 / 11 = LDS-DMA 4-wave co-tenant forms that differ in how the
     DMA pieces are issued -- 10 is the one the pipeline uses --, 2 = register-staged) on the
     same operands in THIS process's precision mode (run in a child with MS_PRECISION=fp16 for the single-pass instantiations):
     bit-identical outputs, ragged edges included."""
@@ -357,7 +357,7 @@ def gemm_variants_equal() -> None:
         ws = torch.empty(lib.ms_linear_split_workspace_bytes(M, K, N), dtype=torch.uint8, device="cuda")
         ys = []
         try:
-            for variant in (0, 7, 8, 10, 11, 2):
+            for variant in (0, 7, 8, 9, 10, 11, 2):
                 lib.ms_gemm_set_variant(variant)
                 y = torch.full((M + 1, N), float("nan"), device="cuda")
                 _lib.check(lib.ms_linear_split_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), M, K, N, act, 0.0, 1.5,

@@ -229,6 +229,36 @@ def test_a_non_finite_input_stays_in_its_row_or_column(lib, M, K, N, flags):
         assert bits_equal(np.ascontiguousarray(got[:, rest]), np.ascontiguousarray(finite[:, rest])), ("Inf in w", n0, k0, "other columns")
 
 
+@pytest.mark.parametrize("M,K,N,flags", [(130, 100, 129, None), (129, 641, 29, 0)])
+def test_a_nan_survives_the_clamp_in_its_row_or_column(lib, M, K, N, flags):
+    """The same contract through MS_ACT_CLAMP, which is torch.nn.Hardtanh: a NaN stays a NaN (``fminf(fmaxf(v, lo), hi)``
+    would make it ``lo``), in the tile kernel's epilogue and in the K-slice reduction; every other element keeps its bits."""
+    x, w, b = C.make("gauss", M, K, N)
+    bd, act = dev(b), (-0.5, 0.5)
+
+    def run(xa, wa, what):
+        if flags is None:
+            return linear(lib, dev(xa), dev(wa), bd, M, K, N, act, what)
+        return splitk(lib, dev(xa), dev(wa), bd, M, K, N, act, flags, what)
+
+    finite = run(x, w, "finite")
+    assert np.isfinite(finite).all() and (np.abs(finite) < 0.5).any() and (finite == 0.5).any() and (finite == -0.5).any()
+    for m0, k0 in ((0, 0), (M - 1, K - 1), (M // 2 + 1, K // 2 + 1)):
+        xn = x.copy()
+        xn[m0, k0] = np.nan
+        got = run(xn, w, ("NaN in x", m0, k0))
+        assert np.isnan(got[m0]).all(), ("NaN in x", m0, k0, "its row")
+        rest = np.arange(M) != m0
+        assert bits_equal(got[rest], finite[rest]), ("NaN in x", m0, k0, "other rows")
+    for n0, k0 in ((0, K - 1), (N - 1, 0), (N // 2 + 1, K // 2 + 1)):
+        wn = w.copy()
+        wn[n0, k0] = np.nan
+        got = run(x, wn, ("NaN in w", n0, k0))
+        assert np.isnan(got[:, n0]).all(), ("NaN in w", n0, k0, "its column")
+        rest = np.arange(N) != n0
+        assert bits_equal(np.ascontiguousarray(got[:, rest]), np.ascontiguousarray(finite[:, rest])), ("NaN in w", n0, k0, "other columns")
+
+
 # ----------------------------------------------------------------------------- the training node
 def test_linear_train_node(lib):
     """``linear_train`` forward and backward at (M, K, N) = (37, 20, 9) against float64 autograd: y and dx, dW, db are each

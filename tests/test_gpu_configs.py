@@ -8,7 +8,7 @@ MI355X: -m gpu.
   2 x LSTM-1024 predictor, joint 512, T = 501 against answers of the numpy oracle stored by
   tests/golden/gen_rnnt_cfg4.py, plus determinism and shard properties over all sixteen utterances;
 * configs[4] (chunked streaming): batch 64 on 32-frame chunks with the state carried, against the REFERENCE run chunk by
-  chunk (tests/golden/cfg5_stream_n64_summary.npz), in the default bf16x3 arithmetic at the north-star's 1e-3 and in a
+  chunk (tests/golden/cfg5_stream_n64_summary.npz), in the default arithmetic (f16x3) at the north-star's 1e-3 and in a
   child process with ``MS_PRECISION=fp16`` ("fp16 MFMA" is what BASELINE.json names) at the fp16 tolerance stated there.
 """
 import os
@@ -170,7 +170,7 @@ def test_wide_workgroup_lstm_fp16_form_vs_oracle_in_subprocess():
 
 def test_split_gemm_kernels_agree_in_both_operand_modes():
     """kernel4 (8 waves), kernel4n (4 waves, the co-tenant form of the two-in-flight pipeline) and kernel2 (register staging):
-    bit-identical in the default bf16x3 mode and, in a child, in the single-pass fp16 mode of configs[4]."""
+    bit-identical in the default mode (f16x3) and, in a child, in the single-pass fp16 mode of configs[4]."""
     cfg_checks.gemm_variants_equal()
     out = _child("gemm_variants_equal()", MS_PRECISION="fp16")
     assert "gemm variants equal in mode fp16" in out

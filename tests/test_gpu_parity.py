@@ -1156,7 +1156,8 @@ def test_beam_one_output_per_batch_element_on_garbage():
 @pytest.mark.parametrize("M,K,N", [(300, 64, 200), (257, 2048, 129), (1000, 640, 8192)])
 @pytest.mark.parametrize("act", [None, (0.0, 20.0)])
 def test_linear_split_bf16x3(lib, M, K, N, act):
-    """x.w as x_hi.w_hi + x_lo.w_hi + x_hi.w_lo: within 1e-5 of |x|.|w| per output."""
+    """x.w as x_hi.w_hi + x_lo.w_hi + x_hi.w_lo in the process's mode (f16x3 by default; the name is from the rounds when bf16x3
+    was): within 1e-5 of |x|.|w| per output.  The exact criterion is tests/test_gemm_split_gpu.py."""
     from myrtlespeech_amd import _lib
     rng = np.random.default_rng(M + K + N)
     x = rng.normal(size=(M, K)).astype(np.float32)
