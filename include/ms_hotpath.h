@@ -987,8 +987,31 @@ int ms_rnnt_align_joint(const float* enc_p, const float* pred_p, const float* w_
  * (ms_embedding_forward's clamping rule), added in the order of r by one workgroup per table row: deterministic bits,
  * rows never looked up are written as zeros.  d_out [R, D], idx [R] int32, d_table [V1, D].
  *
+ * Bidirectional layers (OWN specification; restated by tests/bilstm_backward_ref.py).  One layer of a bidirectional
+ * torch.nn.LSTM is two such cells on the same x with their own weights.  Direction 0 is the recurrence above.  Direction 1
+ * (reverse) is, for sequence n, the same cell run from t = lens[n] - 1 down to 0: h_prev(t) = h[t + 1] for t + 1 < lens[n]
+ * and h0[1][n] at t = lens[n] - 1 (c_prev alike); its h_n / c_n is the state at t = 0.  Its backward therefore runs t = 0 up
+ * to lens[n] - 1: d_hn / d_cn enter at t = 0 with no recurrent term there, dh_t = d_out[t] + dG_{t-1} w_hh,
+ * d_h0[n] = dG[lens[n] - 1, n] w_hh (the row differs per sequence) and d_c0[n] = f dc at lens[n] - 1.  lens as above; rows
+ * t >= lens[n] of dG are exact zeros in both directions.
+ *
+ * ms_lstm_recompute_dir is ms_lstm_recompute with `reverse`: h is that direction's [T,N,H] output, contiguous; reverse = 0
+ * gives ms_lstm_recompute's bits (it is the same call).  With reverse = 1 the recurrent plane is the product of h[t + 1]
+ * into rows 0 .. T - 2 and of h0 into row T - 1, the one row that product leaves free, so the workspace is
+ * ms_lstm_recompute_workspace_bytes; the scan walks t downward with c in a register and takes the h0 row at
+ * t = lens[n] - 1 (without h0 the bias alone, as at step 0 of direction 0).
+ *
+ * ms_lstm_backward_steps_bidir runs both recurrences in the same launches.  gates [2,T,N,4H], c [2,T,N,H] (direction
+ * major: the two ms_lstm_recompute_dir results), c0 / d_hn / d_cn [2,N,H] or NULL, d_out [T,N,2H] as autograd hands the
+ * layer's output gradient over -- direction d is read at column d H + j, no slicing pass.  Outputs dG [2,T,N,4H], d_h0 and
+ * d_c0 [2,N,H], d_b [2,4H], all fully written.  max_len + 1 launches of grid (ceil(H / 32), 2): launch s serves
+ * t = max_len - 1 - s of direction 0 and t = s of direction 1, the last one the two d_h0 products (direction 1 reads the A
+ * row of sequence n at lens[n] - 1).  It is the step kernel of ms_lstm_backward_steps with a direction index, and keeps
+ * every promise above: stream order only, no atomics, float32 MFMA over K = 4H, the same bits on every run; direction 0's
+ * outputs are ms_lstm_backward_steps' bits.
+ *
  * Errors: NULL pointers (other than the optional ones above) and non-positive shapes MS_ERR_INVALID, a short workspace
- * MS_ERR_WORKSPACE.  Out of scope: bidirectional layers, GRU / tanh cells, a single-launch recurrence, mixed precision. */
+ * MS_ERR_WORKSPACE.  Out of scope: GRU / tanh cells, a single-launch recurrence, mixed precision. */
 size_t ms_lstm_recompute_workspace_bytes(int T, int N, int H);
 int ms_lstm_recompute(const float* x, const float* h, const float* h0, const float* c0, const int32_t* lens,
                       const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* gates, float* c,
@@ -996,6 +1019,13 @@ int ms_lstm_recompute(const float* x, const float* h, const float* h0, const flo
 int ms_lstm_backward_steps(const float* gates, const float* c, const float* c0, const float* w_hh, const float* d_out,
                            const float* d_hn, const float* d_cn, const int32_t* lens, int max_len, float* dG, float* d_h0,
                            float* d_c0, float* d_b, int T, int N, int H, void* stream);
+int ms_lstm_recompute_dir(const float* x, const float* h, const float* h0, const float* c0, const int32_t* lens,
+                          const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* gates, float* c,
+                          int T, int N, int In, int H, int reverse, void* workspace, size_t workspace_bytes, void* stream);
+int ms_lstm_backward_steps_bidir(const float* gates, const float* c, const float* c0, const float* w_hh_fwd,
+                                 const float* w_hh_rev, const float* d_out, const float* d_hn, const float* d_cn,
+                                 const int32_t* lens, int max_len, float* dG, float* d_h0, float* d_c0, float* d_b, int T,
+                                 int N, int H, void* stream);
 int ms_embedding_backward(const float* d_out, const int32_t* idx, float* d_table, int R, int D, int V1, void* stream);
 
 #ifdef __cplusplus

@@ -1,6 +1,7 @@
-// Backward through time of one unidirectional torch.nn.LSTM layer (gate order i, f, g, o; weights in torch layout, no
-// packed copy), and the embedding backward beside it.  OWN specification: the comment on ms_lstm_recompute in
-// include/ms_hotpath.h; tests/lstm_backward_ref.py restates it in float64 numpy.
+// Backward through time of one torch.nn.LSTM layer, unidirectional or bidirectional (gate order i, f, g, o; weights in torch
+// layout, no packed copy), and the embedding backward beside it.  OWN specification: the comment on ms_lstm_recompute in
+// include/ms_hotpath.h; tests/lstm_backward_ref.py restates it in float64 numpy, tests/bilstm_backward_ref.py the reverse
+// direction (the same cell walked from lens[n] - 1 down to 0).
 //
 // The forward kernels (rnn.hip) save no gates.  ms_lstm_recompute rebuilds them from what the forward returns: every
 // h_{t-1} is known, so the pre-activations of ALL steps are two batch products over T*N rows on the exact float32 MFMA
@@ -12,6 +13,10 @@
 // the same bits on every run.  The product dh = dG_{t+1} w_hh (K = 4H) runs on v_mfma_f32_32x32x2_f32: gate gradients sit
 // below fp16's normal range, where the hi + lo planes used elsewhere lose what the split exists to keep.  w_hh [4H, H] is
 // contiguous in j, so a wave's B operand is 32 consecutive floats of a row, read as stored.
+//
+// ms_lstm_backward_steps_bidir is the same kernel on a (ceil(H / 32), 2) grid: blockIdx.y picks a direction's argument block,
+// launch s serves t = max_len - 1 - s of the forward direction and t = s of the reverse one.  The two are independent, so a
+// latency-bound loop of 2 (max_len + 1) launches becomes max_len + 1, with every promise above kept.
 #include "common.h"
 
 namespace ms {
@@ -32,23 +37,29 @@ __device__ __forceinline__ int seq_len(const int32_t* lens, int n, int T) {
   return lens ? min(max(lens[n], 0), T) : T;
 }
 
-// gates [T,N,4H] (activated) and c [T,N,H] for t < len[n]; rows past the length are left alone.
+// gates [T,N,4H] (activated) and c [T,N,H] for t < len[n]; rows past the length are left alone.  The scan visits a
+// sequence's steps in the direction's own order: t = 0 .. len - 1, or (reverse) t = len - 1 .. 0.  p2 row t holds the product
+// with the direction's previous output (h[t - 1], reverse h[t + 1]) and row `h0_row` (0, reverse T - 1: the one row that
+// product leaves free) the product with h0, which the first step visited takes instead.
 __global__ __launch_bounds__(256) void lstm_scan_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                         const float* __restrict__ b_hh, const float* __restrict__ c0,
                                                         const int32_t* __restrict__ lens, float* __restrict__ gates,
-                                                        float* __restrict__ c, int T, int N, int H, int have_h0) {
+                                                        float* __restrict__ c, int T, int N, int H, int have_h0, int reverse) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (size_t)N * H) return;
   const int n = (int)(idx / H), j = (int)(idx % H);
   const int len = seq_len(lens, n, T);
+  const int h0_row = reverse ? T - 1 : 0;
   float cprev = c0 ? c0[idx] : 0.f;
-  for (int t = 0; t < len; ++t) {
+  for (int s = 0; s < len; ++s) {
+    const int t = reverse ? len - 1 - s : s;
     const size_t base = ((size_t)t * N + n) * 4 * H + j;
+    const size_t rbase = ((size_t)(s == 0 ? h0_row : t) * N + n) * 4 * H + j;
     float pre[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      // (step 0 from a zero state: the recurrent product is 0 and only its bias remains)
-      const float rec = (t == 0 && !have_h0) ? (b_hh ? b_hh[g * H + j] : 0.f) : p2[base + (size_t)g * H];
+      // (first step from a zero state: the recurrent product is 0 and only its bias remains)
+      const float rec = (s == 0 && !have_h0) ? (b_hh ? b_hh[g * H + j] : 0.f) : p2[rbase + (size_t)g * H];
       pre[g] = p1[base + (size_t)g * H] + rec;
     }
     const float gi = sigmoid_exact(pre[0]), gf = sigmoid_exact(pre[1]), gg = tanhf(pre[2]), go = sigmoid_exact(pre[3]);
@@ -62,17 +73,48 @@ __global__ __launch_bounds__(256) void lstm_scan_kernel(const float* __restrict_
   }
 }
 
-// One step t of the backward recurrence (t == -1: the product alone, written to d_h0).  grid = ceil(H / LB_JT).
-// dg_next = dG_{t+1} [N, 4H], or NULL at the first launch (t == max_len - 1: nothing flows in from later steps).
-__global__ __launch_bounds__(LB_THREADS) void lstm_bwd_step_kernel(const float* __restrict__ gates, const float* __restrict__ c,
-                                                            const float* __restrict__ c0, const float* __restrict__ w_hh,
-                                                            const float* __restrict__ d_out, const float* __restrict__ d_hn,
-                                                            const float* __restrict__ d_cn, const int32_t* __restrict__ lens,
-                                                            const float* __restrict__ dg_next, float* __restrict__ dG,
-                                                            float* __restrict__ d_h0, float* __restrict__ dc_buf,
-                                                            float* __restrict__ d_b, int t, int T, int N, int H, int first) {
+// One direction's share of a step launch.  Forward (reverse == 0) walks t downward and `dg_prev` is dG_{t+1}; reverse walks t
+// upward and it is dG_{t-1}: in both it is the step the launch before this one wrote, or NULL at the first launch (nothing has
+// flowed in yet).  t == -1 is the last launch: the product alone, written to d_h0.
+struct LbDir {
+  const float* gates;      // [T, N, 4H]
+  const float* c;          // [T, N, H]
+  const float* c0;         // [N, H] or NULL
+  const float* w_hh;       // [4H, H]
+  const float* d_out;      // this direction's first column of the output gradient; rows are `ldo` apart
+  const float* d_hn;       // [N, H] or NULL
+  const float* d_cn;       // [N, H] or NULL
+  const float* dg_prev;    // [N, 4H] or NULL
+  float* dG;               // [T, N, 4H]
+  float* d_h0;             // [N, H]
+  float* dc_buf;           // [N, H]: dc carried between the launches; what the last live step leaves is d_c0
+  float* d_b;              // [4H]
+  int t;
+  int reverse;
+};
+struct LbStep {
+  LbDir dir[2];            // blockIdx.y picks one
+};
+
+// One step of the backward recurrence for the directions of `step`.  grid = (ceil(H / LB_JT), directions).
+__global__ __launch_bounds__(LB_THREADS) void lstm_bwd_step_kernel(const LbStep step, const int32_t* __restrict__ lens, int ldo,
+                                                                   int T, int N, int H, int first) {
   __shared__ float part[LB_WAVES][LB_NT][LB_PS];
   __shared__ float red[LB_ROWG][4][LB_JT];
+  const LbDir& d = step.dir[blockIdx.y];
+  const float* __restrict__ gates = d.gates;
+  const float* __restrict__ c = d.c;
+  const float* __restrict__ c0 = d.c0;
+  const float* __restrict__ w_hh = d.w_hh;
+  const float* __restrict__ d_out = d.d_out;
+  const float* __restrict__ d_hn = d.d_hn;
+  const float* __restrict__ d_cn = d.d_cn;
+  const float* __restrict__ dg_prev = d.dg_prev;
+  float* __restrict__ dG = d.dG;
+  float* __restrict__ d_h0 = d.d_h0;
+  float* __restrict__ dc_buf = d.dc_buf;
+  float* __restrict__ d_b = d.d_b;
+  const int t = d.t, reverse = d.reverse;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, half = lane >> 5;
@@ -80,22 +122,34 @@ __global__ __launch_bounds__(LB_THREADS) void lstm_bwd_step_kernel(const float* 
   const size_t K4 = (size_t)4 * H;
   const int ej = j0 + (tid & 31);       // the unit this thread serves in the elementwise phase
   const int erow = tid >> 5;            // ... and its rows erow + LB_ROWG i of a pass
+  // the reverse direction's d_h0 is the product with each sequence's OWN last row of dG
+  const bool own_rows = reverse && t < 0;
+  const bool product = dg_prev != nullptr || own_rows;
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
 
   for (int r0 = 0; r0 < N; r0 += LB_NT) {
-    if (dg_next != nullptr) {
+    if (product) {
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
       const int arow = r0 + l31;
       const int bcol = j0 + l31;
+      const float* ap = nullptr;        // this lane's row of the A operand (NULL: a row of zeros)
+      if (arow < N) {
+        if (own_rows) {
+          const int len = seq_len(lens, arow, T);
+          if (len > 0) ap = dG + ((size_t)(len - 1) * N + arow) * K4;
+        } else {
+          ap = dg_prev + (size_t)arow * K4;
+        }
+      }
       const int noct = (H + 1) / 2;     // k-octets: 4H / 8 rounded up
       for (int q = wave; q < noct; q += LB_WAVES) {
         const int kq = 2 * q + half;    // this lane half's k-quad; quads exist for kq < H
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
         float b[4] = {0.f, 0.f, 0.f, 0.f};
         if (kq < H) {
-          if (arow < N) a = *reinterpret_cast<const f32x4*>(dg_next + (size_t)arow * K4 + (size_t)4 * kq);
+          if (ap != nullptr) a = *reinterpret_cast<const f32x4*>(ap + (size_t)4 * kq);
           if (bcol < H) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) b[e] = w_hh[((size_t)4 * kq + e) * H + bcol];
@@ -114,7 +168,7 @@ __global__ __launch_bounds__(LB_THREADS) void lstm_bwd_step_kernel(const float* 
       const int n = r0 + rr;
       if (n >= N || ej >= H) continue;
       float dh = 0.f;
-      if (dg_next != nullptr) {
+      if (product) {
 #pragma unroll
         for (int w = 0; w < LB_WAVES; ++w) dh += part[w][rr][tid & 31];
       }
@@ -133,12 +187,15 @@ __global__ __launch_bounds__(LB_THREADS) void lstm_bwd_step_kernel(const float* 
         continue;
       }
       const size_t tnj = ((size_t)t * N + n) * H + ej;
-      dh += d_out[tnj];
-      const bool last = (t == len - 1);
+      dh += d_out[((size_t)t * N + n) * ldo + ej];
+      // the step at which the final states' gradients enter: the one the direction's forward ended on
+      const bool last = reverse ? (t == 0) : (t == len - 1);
       if (last && d_hn) dh += d_hn[nj];
       float dc = last ? (d_cn ? d_cn[nj] : 0.f) : dc_buf[nj];
       const float gi = gates[grow], gf = gates[grow + (size_t)H], gg = gates[grow + (size_t)2 * H], go = gates[grow + (size_t)3 * H];
-      const float cprev = t > 0 ? c[tnj - (size_t)N * H] : (c0 ? c0[nj] : 0.f);
+      float cprev;
+      if (reverse) cprev = t + 1 < len ? c[tnj + (size_t)N * H] : (c0 ? c0[nj] : 0.f);
+      else cprev = t > 0 ? c[tnj - (size_t)N * H] : (c0 ? c0[nj] : 0.f);
       const float tc = tanhf(c[tnj]);
       dc += dh * go * (1.f - tc * tc);
       const float dgi = dc * gg * gi * (1.f - gi);
@@ -195,11 +252,13 @@ extern "C" size_t ms_lstm_recompute_workspace_bytes(int T, int N, int H) {
   return 2 * ms::align_up((size_t)T * N * 4 * H * sizeof(float), 256);
 }
 
-extern "C" int ms_lstm_recompute(const float* x, const float* h, const float* h0, const float* c0, const int32_t* lens,
-                                 const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* gates,
-                                 float* c, int T, int N, int In, int H, void* workspace, size_t workspace_bytes, void* stream_) {
+extern "C" int ms_lstm_recompute_dir(const float* x, const float* h, const float* h0, const float* c0, const int32_t* lens,
+                                     const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* gates,
+                                     float* c, int T, int N, int In, int H, int reverse, void* workspace, size_t workspace_bytes,
+                                     void* stream_) {
   MS_REQUIRE(x && h && w_ih && w_hh && gates && c, "null pointer");
   MS_REQUIRE(T > 0 && N > 0 && In > 0 && H > 0, "bad shape");
+  MS_REQUIRE(reverse == 0 || reverse == 1, "reverse must be 0 or 1");
   MS_REQUIRE((size_t)T * N < ((size_t)1 << 31) / 4 / (size_t)H, "T N 4H exceeds the GEMM's int extents");
   MS_REQUIRE(workspace != nullptr, "null workspace");
   if (workspace_bytes < ms_lstm_recompute_workspace_bytes(T, N, H)) {
@@ -208,23 +267,32 @@ extern "C" int ms_lstm_recompute(const float* x, const float* h, const float* h0
   }
   hipStream_t st = (hipStream_t)stream_;
   const size_t plane = ms::align_up((size_t)T * N * 4 * H * sizeof(float), 256) / sizeof(float);
+  const size_t row = (size_t)N * 4 * H;
   float* p1 = (float*)workspace;
   float* p2 = p1 + plane;
   int rc = ms::linear_launch(x, w_ih, b_ih, p1, T * N, In, 4 * H, MS_ACT_NONE, 0.f, 0.f, st);
   if (rc != MS_OK) return rc;
-  if (h0 != nullptr) {
-    rc = ms::linear_launch(h0, w_hh, b_hh, p2, N, H, 4 * H, MS_ACT_NONE, 0.f, 0.f, st);
+  if (h0 != nullptr) {      // the row the shifted product below leaves free: 0, or T - 1 in the reverse direction
+    rc = ms::linear_launch(h0, w_hh, b_hh, p2 + (reverse ? (size_t)(T - 1) * row : 0), N, H, 4 * H, MS_ACT_NONE, 0.f, 0.f, st);
     if (rc != MS_OK) return rc;
   }
-  if (T > 1) {      // rows t >= 1 of the recurrent plane come from h[t - 1]
-    rc = ms::linear_launch(h, w_hh, b_hh, p2 + (size_t)N * 4 * H, (T - 1) * N, H, 4 * H, MS_ACT_NONE, 0.f, 0.f, st);
+  if (T > 1) {      // rows t >= 1 of the recurrent plane come from h[t - 1]; reverse: rows t <= T - 2 from h[t + 1]
+    rc = ms::linear_launch(h + (reverse ? (size_t)N * H : 0), w_hh, b_hh, p2 + (reverse ? 0 : row), (T - 1) * N, H, 4 * H,
+                           MS_ACT_NONE, 0.f, 0.f, st);
     if (rc != MS_OK) return rc;
   }
   const size_t cells = (size_t)N * H;
   hipLaunchKernelGGL(ms::lstm_scan_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, p1, p2, b_hh, c0, lens, gates,
-                     c, T, N, H, h0 != nullptr ? 1 : 0);
+                     c, T, N, H, h0 != nullptr ? 1 : 0, reverse);
   MS_LAUNCH_CHECK();
   return MS_OK;
+}
+
+extern "C" int ms_lstm_recompute(const float* x, const float* h, const float* h0, const float* c0, const int32_t* lens,
+                                 const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* gates,
+                                 float* c, int T, int N, int In, int H, void* workspace, size_t workspace_bytes, void* stream_) {
+  return ms_lstm_recompute_dir(x, h, h0, c0, lens, w_ih, w_hh, b_ih, b_hh, gates, c, T, N, In, H, 0, workspace, workspace_bytes,
+                               stream_);
 }
 
 extern "C" int ms_lstm_backward_steps(const float* gates, const float* c, const float* c0, const float* w_hh,
@@ -240,12 +308,52 @@ extern "C" int ms_lstm_backward_steps(const float* gates, const float* c, const 
   const size_t row = (size_t)N * 4 * H;
   if (max_len < T) MS_HIP(hipMemsetAsync(dG + (size_t)max_len * row, 0, (size_t)(T - max_len) * row * sizeof(float), st));
   const dim3 grid((unsigned)ms::cdiv(H, ms::LB_JT));
+  ms::LbStep step = {};
+  step.dir[0] = ms::LbDir{gates, c, c0, w_hh, d_out, d_hn, d_cn, nullptr, dG, d_h0, d_c0, d_b, 0, 0};
   for (int t = max_len - 1; t >= -1; --t) {
     const int first = (t == max_len - 1) ? 1 : 0;
     // (T == 1 or max_len == 1: the d_h0 launch follows the first step directly and still reads dG_0)
-    const float* dg_next = (first && t >= 0) ? nullptr : dG + (size_t)(t + 1) * row;
-    hipLaunchKernelGGL(ms::lstm_bwd_step_kernel, grid, dim3(ms::LB_THREADS), 0, st, gates, c, c0, w_hh, d_out, d_hn, d_cn, lens, dg_next, dG,
-                       d_h0, d_c0, d_b, t, T, N, H, first);
+    step.dir[0].dg_prev = (first && t >= 0) ? nullptr : dG + (size_t)(t + 1) * row;
+    step.dir[0].t = t;
+    hipLaunchKernelGGL(ms::lstm_bwd_step_kernel, grid, dim3(ms::LB_THREADS), 0, st, step, lens, H, T, N, H, first);
+  }
+  MS_LAUNCH_CHECK();
+  return MS_OK;
+}
+
+extern "C" int ms_lstm_backward_steps_bidir(const float* gates, const float* c, const float* c0, const float* w_hh_fwd,
+                                            const float* w_hh_rev, const float* d_out, const float* d_hn, const float* d_cn,
+                                            const int32_t* lens, int max_len, float* dG, float* d_h0, float* d_c0, float* d_b,
+                                            int T, int N, int H, void* stream_) {
+  MS_REQUIRE(gates && c && w_hh_fwd && w_hh_rev && d_out && dG && d_h0 && d_c0 && d_b, "null pointer");
+  MS_REQUIRE(T > 0 && N > 0 && H > 0, "bad shape");
+  MS_REQUIRE(max_len >= 1 && max_len <= T, "max_len outside [1, T]");
+  MS_REQUIRE(lens != nullptr || max_len == T, "without lens every sequence has T steps: max_len must be T");
+  // (both halves of dG are read in 16-byte quads: T N 4H floats apart, so one test covers them)
+  MS_REQUIRE(((uintptr_t)dG & 15) == 0, "dG must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream_;
+  const size_t row = (size_t)N * 4 * H;
+  const size_t nh = (size_t)N * H;
+  const size_t plane = (size_t)T * row;       // one direction of gates / dG; c is plane / 4
+  float* dG_rev = dG + plane;
+  if (max_len < T) {
+    const size_t bytes = (size_t)(T - max_len) * row * sizeof(float);
+    MS_HIP(hipMemsetAsync(dG + (size_t)max_len * row, 0, bytes, st));
+    MS_HIP(hipMemsetAsync(dG_rev + (size_t)max_len * row, 0, bytes, st));
+  }
+  const dim3 grid((unsigned)ms::cdiv(H, ms::LB_JT), 2);
+  ms::LbStep step;
+  step.dir[0] = ms::LbDir{gates, c, c0, w_hh_fwd, d_out, d_hn, d_cn, nullptr, dG, d_h0, d_c0, d_b, 0, 0};
+  step.dir[1] = ms::LbDir{gates + plane, c + plane / 4, c0 ? c0 + nh : nullptr, w_hh_rev, d_out + H, d_hn ? d_hn + nh : nullptr,
+                          d_cn ? d_cn + nh : nullptr, nullptr, dG_rev, d_h0 + nh, d_c0 + nh, d_b + (size_t)4 * H, 0, 1};
+  // launch s: the forward direction's step max_len - 1 - s beside the reverse direction's step s; launch max_len: both d_h0
+  for (int s = 0; s <= max_len; ++s) {
+    const bool tail = s == max_len;
+    step.dir[0].t = tail ? -1 : max_len - 1 - s;
+    step.dir[1].t = tail ? -1 : s;
+    step.dir[0].dg_prev = s == 0 ? nullptr : dG + (size_t)(max_len - s) * row;
+    step.dir[1].dg_prev = s == 0 ? nullptr : dG_rev + (size_t)(s - 1) * row;      // (not read by the d_h0 launch: own rows)
+    hipLaunchKernelGGL(ms::lstm_bwd_step_kernel, grid, dim3(ms::LB_THREADS), 0, st, step, lens, 2 * H, T, N, H, s == 0 ? 1 : 0);
   }
   MS_LAUNCH_CHECK();
   return MS_OK;

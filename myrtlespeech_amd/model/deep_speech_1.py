@@ -48,9 +48,44 @@ class DeepSpeech1(torch.nn.Module):
             layers.append(torch.nn.Dropout(p=self._drop_prob))
         return layers[0] if len(layers) == 1 else torch.nn.Sequential(*layers)
 
-    def forward(self, x: Tuple[torch.Tensor, torch.Tensor], hx: Optional[RNNState] = None
+    def _forward_train(self, x: Tuple[torch.Tensor, torch.Tensor], hx: Optional[RNNState]):
+        """``forward`` as a chain of autograd nodes on the device (``model/rnn_autograd.py``): every Linear through the
+        exact float32 product with its clamp fused, the bidirectional LSTM through ``rnn_train``.  The input features are
+        data: no gradient is returned for them."""
+        from myrtlespeech_amd.model.rnn_autograd import linear_clamp_train, linear_train
+        if isinstance(self.bi_lstm, HardLSTM):
+            raise ValueError("DeepSpeech1.forward(differentiable=True) does not serve hard_lstm=True (HardLSTM has no backward)")
+        if self.training and self._drop_prob > 0:
+            raise ValueError("DeepSpeech1.forward(differentiable=True) does not serve dropout masks: train in .eval() or with "
+                             "drop_prob = 0")
+        h, seq_lens = x
+        if h.dim() != 4 or h.shape[1] * h.shape[2] != self.fc1[0].in_features or min(h.shape) <= 0:
+            raise ValueError(f"the input must be [batch, {self.input_channels}, {self.input_features}, seq_len], got {tuple(h.shape)}")
+        _lib.require_gpu()
+        h = _lib.f32c(h.detach())
+        n, c, f, t = h.shape
+        tnf = torch.empty((t, n, c * f), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.load().ms_nct_to_tnc(_lib.ptr(h), _lib.ptr(tnf), n, c * f, t, _lib.stream_ptr()),
+                   "ms_nct_to_tnc")
+        h = tnf.reshape(t * n, c * f)
+        for fc in (self.fc1, self.fc2, self.fc3):
+            h = linear_clamp_train(h, fc[0], 0.0, self._relu_clip)
+        # bi_lstm is batch_first: hand it the batch-major view, as the default path does
+        (h, _), hid = self.bi_lstm((h.reshape(t, n, -1).transpose(0, 1), seq_lens), hx, differentiable=True)
+        h = h.transpose(0, 1).reshape(t * n, -1)
+        h = linear_clamp_train(h, self.fc4[0], 0.0, self._relu_clip)
+        out = linear_train(h, self.out).reshape(t, n, -1)
+        return (out, _lib.lens_to_device(seq_lens)), hid
+
+    def forward(self, x: Tuple[torch.Tensor, torch.Tensor], hx: Optional[RNNState] = None, differentiable: bool = False
                 ) -> Tuple[Tuple[torch.Tensor, torch.Tensor], RNNState]:
-        """``[batch, channels, features, seq_len] -> ([seq_len, batch, out_features], lens), hid``."""
+        """``[batch, channels, features, seq_len] -> ([seq_len, batch, out_features], lens), hid``.
+
+        ``differentiable=True``: the same chain and the same structure as autograd nodes on the device, so
+        ``CTCLoss()((out, lens), (y, y_lens)).backward()`` fills the gradient of every parameter; ValueError for
+        ``hard_lstm=True`` and for ``drop_prob > 0`` in training mode.  The default path is untouched."""
+        if differentiable:
+            return self._forward_train(x, hx)
         _lib.require_gpu()
         h, seq_lens = x
         h = _lib.f32c(h)

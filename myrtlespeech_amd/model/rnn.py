@@ -372,10 +372,21 @@ class RNN(torch.nn.Module):
             out.append(dirs)
         return out
 
-    def forward(self, x: Tuple[RNNData, Lengths], hx: Optional[RNNState] = None
+    def forward(self, x: Tuple[RNNData, Lengths], hx: Optional[RNNState] = None, differentiable: bool = False
                 ) -> Tuple[Tuple[RNNData, Lengths], RNNState]:
         """``((out, lengths), hid)`` exactly as rnn.py:133-185: rows past each
-        sequence's length are 0, ``hid`` holds each sequence's last valid state."""
+        sequence's length are 0, ``hid`` holds each sequence's last valid state.
+
+        ``differentiable=True``: the same values as an autograd node (``rnn_autograd.rnn_train``; LSTM stacks only, refused
+        with ValueError otherwise), so a loss reaches the input, ``hx`` and every parameter.  ``batch_first`` is two torch
+        transposes, which autograd sees.  The default path is untouched."""
+        if differentiable:
+            from myrtlespeech_amd.model.rnn_autograd import rnn_train      # (that module imports this one)
+            inp, lengths = x
+            if inp.dim() != 3:
+                raise ValueError(f"the input must have three dimensions, got {tuple(inp.shape)}")
+            out, hid = rnn_train(self, inp.transpose(0, 1) if self.batch_first else inp, lengths, hx)
+            return (out.transpose(0, 1) if self.batch_first else out, lengths), hid
         _lib.require_gpu()
         inp, lengths = x
         if self.training and self.rnn.dropout > 0 and self.rnn.num_layers > 1:

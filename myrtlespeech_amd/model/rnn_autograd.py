@@ -1,4 +1,4 @@
-"""Training pieces for the transducer's prediction network -- this repository's OWN specification (the comment on
+"""Training pieces for the transducer's prediction network and for DeepSpeech1 -- this repository's OWN specification (the comment on
 ``ms_lstm_recompute`` in include/ms_hotpath.h; tests/lstm_backward_ref.py restates it in numpy).
 
 ``lstm_train(rnn, x, lens, hx)`` is ``RNN.forward`` on a unidirectional LSTM stack as an autograd node.  The forward is the
@@ -13,9 +13,17 @@ rebuilds them per layer, top down (``ms_lstm_recompute``: two batch GEMMs and a 
 products all run through ``ms_linear_forward`` (db is a ones-row product), and the embedding look-up whose backward is
 ``ms_embedding_backward``.
 
-Out of scope, and refused with ValueError before a device is needed: GRU and tanh cells, ``bidirectional=True``,
-inter-layer dropout in training mode.  There is no backward for the convolutions or the encoder's stacks, no
-single-launch (persistent) backward recurrence and no mixed-precision gradient.
+``rnn_train(rnn, x, lens, hx)`` is the same for LSTM stacks of either kind.  A bidirectional stack's backward runs, per layer,
+two ``ms_lstm_recompute_dir`` calls (the reverse direction's gates from ``h[t + 1]``), ONE ``ms_lstm_backward_steps_bidir``
+(both recurrences in the same launches, the layer's ``[T, N, 2H]`` output gradient read in place) and the batch products per
+direction; tests/bilstm_backward_ref.py restates it.  ``RNN.forward(..., differentiable=True)`` and
+``DeepSpeech1.forward(..., differentiable=True)`` are built on it, the latter with ``linear_clamp_train``: a linear layer with
+its ``Hardtanh`` fused, whose backward passes dy where the saved OUTPUT is strictly inside the clamp.
+
+Out of scope, and refused with ValueError before a device is needed: GRU and tanh cells, ``HardLSTM``, inter-layer dropout
+in training mode (``lstm_train`` also refuses ``bidirectional=True``: ``rnn_train`` serves it).  There is no backward for the
+convolutions, the lookahead or DS2, no dropout mask, no single-launch (persistent) backward recurrence and no mixed-precision
+gradient.
 """
 from typing import Optional, Tuple
 
@@ -102,50 +110,121 @@ class _EmbeddingFunction(torch.autograd.Function):
         return _like(d_table, table), None
 
 
+class _LinearClampFunction(torch.autograd.Function):
+    """y = clamp(x w^T + b, lo, hi) with the clamp fused into the product (``ACT_CLAMP``); backward: dy passes where
+    lo < y < hi strictly -- ``Hardtanh``'s rule, and y sits strictly inside exactly where the pre-activation does, so the
+    saved OUTPUT decides and no pre-activation is kept -- then ``_LinearFunction``'s three products."""
+
+    @staticmethod
+    def forward(ctx, x2d, weight, bias, lo, hi):
+        x = _lib.f32c(x2d.detach())
+        w = _lib.f32c(weight.detach())
+        b = None if bias is None else _lib.f32c(bias.detach())
+        m, k = x.shape
+        n = w.shape[0]
+        y = torch.empty((m, n), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.load().ms_linear_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), m, k, n, _lib.ACT_CLAMP,
+                                                 float(lo), float(hi), _lib.stream_ptr()), "ms_linear_forward")
+        ctx.save_for_backward(x, w, y)
+        ctx.like = (x2d, weight, bias)
+        ctx.clamp = (float(lo), float(hi))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        x_like, w_like, b_like = ctx.like
+        lo, hi = ctx.clamp
+        dy = torch.where((y > lo) & (y < hi), _lib.f32c(dy), torch.zeros((), dtype=torch.float32, device="cuda"))
+        need = ctx.needs_input_grad
+        dx = _like(gemm_nt(dy, w.t()), x_like) if need[0] else None
+        dy_t = dy.t().contiguous() if (need[1] or (b_like is not None and need[2])) else None
+        dw = _like(gemm_nt(dy_t, x.t()), w_like) if need[1] else None
+        db = None
+        if b_like is not None and need[2]:
+            ones = torch.ones((1, dy.shape[0]), dtype=torch.float32, device="cuda")
+            db = _like(gemm_nt(ones, dy_t), b_like)
+        return dx, dw, db, None, None
+
+
+def linear_clamp_train(x2d: torch.Tensor, lin: torch.nn.Linear, lo: float, hi: float) -> torch.Tensor:
+    """``Hardtanh(lo, hi)(lin(x2d))`` for x2d [M, K] as one autograd node on the device."""
+    if not lo < hi:
+        raise ValueError(f"linear_clamp_train needs lo < hi, got [{lo}, {hi}]")
+    return _LinearClampFunction.apply(x2d, lin.weight, lin.bias, lo, hi)
+
+
 def embedding_train(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """idx [...] int32 on the device -> [..., D], differentiable in ``table``."""
     return _EmbeddingFunction.apply(table, idx)
 
 
+def _stack_forward(ctx, ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat):
+    """The forward of both stack nodes: ``run_layers`` one layer at a time, every layer's output kept for the backward."""
+    nl = rnn.rnn.num_layers
+    hidden = rnn.rnn.hidden_size
+    params = rnn._layer_params()
+    xin = _lib.f32c(x.detach())
+    h0d = _lib.f32c(h0.detach()) if has_hx else None
+    c0d = _lib.f32c(c0.detach()) if has_hx else None
+    layer_in, hns, cns = [xin], [], []
+    for layer in range(nl):
+        sl = slice(ndir * layer, ndir * (layer + 1))
+        out, hn, cn = run_layers(_lib.CELL_LSTM, layer_in[-1], lens_dev, max_len, [params[layer]], [rnn._packed[layer]], hidden,
+                                 None if h0d is None else h0d[sl], None if c0d is None else c0d[sl],
+                                 rnn._workspace, rnn.check_status, ragged=ragged)
+        layer_in.append(out.contiguous())
+        hns.append(hn)
+        cns.append(cn)
+    weights = [None if p is None else _lib.f32c(p.detach()) for p in flat]
+    ctx.save_for_backward(*layer_in, *([h0d, c0d] if has_hx else []), *[w for w in weights if w is not None])
+    ctx.meta = dict(nl=nl, hidden=hidden, lens_dev=lens_dev, max_len=max_len, has_hx=has_hx,
+                    has_w=[w is not None for w in weights], like=(x, h0, c0) + tuple(flat))
+    return layer_in[-1], torch.cat(hns, 0), torch.cat(cns, 0)
+
+
+def _stack_saved(ctx):
+    """(layer_in, h0, c0, weights) as ``_stack_forward`` saved them (absent biases back as None)."""
+    m = ctx.meta
+    saved = list(ctx.saved_tensors)
+    layer_in = saved[:m["nl"] + 1]
+    pos = m["nl"] + 1
+    h0 = c0 = None
+    if m["has_hx"]:
+        h0, c0 = saved[pos], saved[pos + 1]
+        pos += 2
+    weights = []
+    for has in m["has_w"]:
+        weights.append(saved[pos] if has else None)
+        pos += has
+    return layer_in, h0, c0, weights
+
+
+def _stack_grads(ctx, d_top, d_h0, d_c0, w_grads):
+    """The backward's return value: gradients shaped and typed like the inputs they belong to, None where none is wanted."""
+    m = ctx.meta
+    x_like, h_like, c_like = m["like"][:3]
+    dx = _like(d_top, x_like) if ctx.needs_input_grad[5] else None
+    dh0 = _like(d_h0, h_like) if (m["has_hx"] and ctx.needs_input_grad[6]) else None
+    dc0 = _like(d_c0, c_like) if (m["has_hx"] and ctx.needs_input_grad[7]) else None
+    flat = []
+    for k, (g, like) in enumerate(zip(w_grads, m["like"][3:])):
+        flat.append(None if (g is None or like is None or not ctx.needs_input_grad[8 + k]) else _like(g, like))
+    return (None, None, None, None, None, dx, dh0, dc0, *flat)
+
+
 class _LSTMStackFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, *flat):
-        nl = rnn.rnn.num_layers
-        hidden = rnn.rnn.hidden_size
-        params = rnn._layer_params()
-        xin = _lib.f32c(x.detach())
-        h0d = _lib.f32c(h0.detach()) if has_hx else None
-        c0d = _lib.f32c(c0.detach()) if has_hx else None
-        layer_in, hns, cns = [xin], [], []
-        for layer in range(nl):
-            out, hn, cn = run_layers(_lib.CELL_LSTM, layer_in[-1], lens_dev, max_len, [params[layer]], [rnn._packed[layer]], hidden,
-                                     None if h0d is None else h0d[layer:layer + 1], None if c0d is None else c0d[layer:layer + 1],
-                                     rnn._workspace, rnn.check_status, ragged=ragged)
-            layer_in.append(out.contiguous())
-            hns.append(hn)
-            cns.append(cn)
-        weights = [None if p is None else _lib.f32c(p.detach()) for p in flat]
-        ctx.save_for_backward(*layer_in, *([h0d, c0d] if has_hx else []), *[w for w in weights if w is not None])
-        ctx.meta = dict(nl=nl, hidden=hidden, lens_dev=lens_dev, max_len=max_len, has_hx=has_hx,
-                        has_w=[w is not None for w in weights], like=(x, h0, c0) + tuple(flat))
-        return layer_in[-1], torch.cat(hns, 0), torch.cat(cns, 0)
+        return _stack_forward(ctx, 1, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out, d_hn, d_cn):
         m = ctx.meta
         nl, hidden, lens_dev, max_len = m["nl"], m["hidden"], m["lens_dev"], m["max_len"]
-        saved = list(ctx.saved_tensors)
-        layer_in = saved[:nl + 1]
-        pos = nl + 1
-        h0 = c0 = None
-        if m["has_hx"]:
-            h0, c0 = saved[pos], saved[pos + 1]
-            pos += 2
-        weights = []
-        for has in m["has_w"]:
-            weights.append(saved[pos] if has else None)
-            pos += has
+        layer_in, h0, c0, weights = _stack_saved(ctx)
         lib = _lib.load()
         t, n, _ = layer_in[0].shape
         rows = t * n
@@ -192,29 +271,94 @@ class _LSTMStackFunction(torch.autograd.Function):
             d_h0s[layer], d_c0s[layer] = d_h0, d_c0
             if layer > 0 or ctx.needs_input_grad[5]:
                 d_top = gemm_nt(g2, w_ih.t()).reshape(t, n, in_size)
-        x_like, h_like, c_like = m["like"][:3]
-        dx = _like(d_top, x_like) if ctx.needs_input_grad[5] else None
-        dh0 = _like(torch.stack(d_h0s, 0), h_like) if (m["has_hx"] and ctx.needs_input_grad[6]) else None
-        dc0 = _like(torch.stack(d_c0s, 0), c_like) if (m["has_hx"] and ctx.needs_input_grad[7]) else None
-        flat = []
-        for k, (g, like) in enumerate(zip(w_grads, m["like"][3:])):
-            flat.append(None if (g is None or like is None or not ctx.needs_input_grad[8 + k]) else _like(g, like))
-        return (None, None, None, None, None, dx, dh0, dc0, *flat)
+        return _stack_grads(ctx, d_top, torch.stack(d_h0s, 0), torch.stack(d_c0s, 0), w_grads)
 
 
-def lstm_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-               ) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
-    """x [T, N, In] time-major, lens [N] sorted descending, hx = (h0, c0) [num_layers, N, H] or None (zeros) ->
-    ``(out [T, N, H], (h_n, c_n))`` with ``RNN.forward``'s values (rows past a length are 0, the states are those at
-    ``lens[n] - 1``), differentiable in x, hx and every parameter of the stack.  ``RNN.forward`` itself is untouched."""
-    if not isinstance(rnn, RNN) or rnn.rnn_type != RNNType.LSTM:
-        raise ValueError("lstm_train serves LSTM stacks only (GRU and tanh cells have no backward in this project)")
-    if rnn.bidirectional:
-        raise ValueError("lstm_train does not serve bidirectional=True (no backward for the reverse direction)")
-    if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
-        raise ValueError("lstm_train does not serve inter-layer dropout in training mode")
-    if rnn.batch_first:
-        raise ValueError("lstm_train takes time-major input (batch_first=False)")
+class _BiLSTMStackFunction(torch.autograd.Function):
+    """``_LSTMStackFunction`` for bidirectional stacks: per layer two ``ms_lstm_recompute_dir`` calls into the halves of
+    gates / c, ONE ``ms_lstm_backward_steps_bidir`` (both recurrences in the same launches) and the batch products per
+    direction.  ``flat`` holds eight tensors per layer: direction 0's (w_ih, w_hh, b_ih, b_hh), then the ``_reverse`` ones."""
+
+    @staticmethod
+    def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, *flat):
+        return _stack_forward(ctx, 2, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out, d_hn, d_cn):
+        m = ctx.meta
+        nl, hidden, lens_dev, max_len = m["nl"], m["hidden"], m["lens_dev"], m["max_len"]
+        layer_in, h0, c0, weights = _stack_saved(ctx)
+        lib = _lib.load()
+        t, n, _ = layer_in[0].shape
+        rows = t * n
+        nbytes = lib.ms_lstm_recompute_workspace_bytes(t, n, hidden)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")                      # transient
+        gates = torch.empty((2, t, n, 4 * hidden), dtype=torch.float32, device="cuda")
+        cells = torch.empty((2, t, n, hidden), dtype=torch.float32, device="cuda")
+        steps = torch.arange(t, device="cuda")[:, None]
+        live = (steps < lens_dev[None, :]).unsqueeze(-1)            # [T, N, 1]: the rows that exist
+        final = (steps == lens_dev[None, :] - 1).unsqueeze(-1)      # ... and each sequence's last one
+        zero = torch.zeros((), dtype=torch.float32, device="cuda")
+        d_top = _lib.f32c(d_out)
+        d_hn = None if d_hn is None else _lib.f32c(d_hn)
+        d_cn = None if d_cn is None else _lib.f32c(d_cn)
+        d_h0s, d_c0s = [None] * nl, [None] * nl
+        w_grads = [None] * (8 * nl)
+        for layer in range(nl - 1, -1, -1):
+            lw = weights[8 * layer:8 * layer + 8]
+            xl, out = layer_in[layer], layer_in[layer + 1]
+            in_size = xl.shape[2]
+            sl = slice(2 * layer, 2 * layer + 2)
+            h0l = None if h0 is None else h0[sl].contiguous()
+            c0l = None if c0 is None else c0[sl].contiguous()
+            hs = [out[..., :hidden].contiguous(), out[..., hidden:].contiguous()]      # each direction's [T, N, H] output
+            for d in (0, 1):
+                w_ih, w_hh, b_ih, b_hh = lw[4 * d:4 * d + 4]
+                _lib.check(lib.ms_lstm_recompute_dir(_lib.ptr(xl), _lib.ptr(hs[d]), _lib.ptr(None if h0l is None else h0l[d]),
+                                                     _lib.ptr(None if c0l is None else c0l[d]), _lib.ptr(lens_dev), _lib.ptr(w_ih),
+                                                     _lib.ptr(w_hh), _lib.ptr(b_ih), _lib.ptr(b_hh), _lib.ptr(gates[d]),
+                                                     _lib.ptr(cells[d]), t, n, in_size, hidden, d, _lib.ptr(ws), ws.numel(),
+                                                     _lib.stream_ptr()), "ms_lstm_recompute_dir")
+            d_g = torch.empty((2, t, n, 4 * hidden), dtype=torch.float32, device="cuda")
+            d_h0 = torch.empty((2, n, hidden), dtype=torch.float32, device="cuda")
+            d_c0 = torch.empty((2, n, hidden), dtype=torch.float32, device="cuda")
+            d_b = torch.empty((2, 4 * hidden), dtype=torch.float32, device="cuda")
+            _lib.check(lib.ms_lstm_backward_steps_bidir(_lib.ptr(gates), _lib.ptr(cells), _lib.ptr(c0l), _lib.ptr(lw[1]), _lib.ptr(lw[5]),
+                                                        _lib.ptr(d_top), _lib.ptr(None if d_hn is None else d_hn[sl].contiguous()),
+                                                        _lib.ptr(None if d_cn is None else d_cn[sl].contiguous()),
+                                                        _lib.ptr(lens_dev), max_len, _lib.ptr(d_g), _lib.ptr(d_h0), _lib.ptr(d_c0),
+                                                        _lib.ptr(d_b), t, n, hidden, _lib.stream_ptr()),
+                       "ms_lstm_backward_steps_bidir")
+            # (dG is exactly 0 in the rows past a length and the layers' outputs are 0 there; what the CALLER left in those
+            # rows of x may be anything, a NaN included, and must not reach the sum)
+            x_rows = (torch.where(live, xl, zero) if layer == 0 else xl).reshape(rows, in_size).t()
+            pad = torch.zeros((1, n, hidden), dtype=torch.float32, device="cuda")
+            # h_prev: direction 0 is h shifted down with h0[0] in row 0; the reverse direction is h shifted UP, and its
+            # initial state sits at each sequence's last live row
+            h_prev = [torch.cat([pad if h0l is None else h0l[0][None], hs[0][:-1]], 0),
+                      torch.where(final, zero if h0l is None else h0l[1][None], torch.cat([hs[1][1:], pad], 0))]
+            need_dx = layer > 0 or ctx.needs_input_grad[5]
+            dx = None
+            for d in (0, 1):
+                g2 = d_g[d].reshape(rows, 4 * hidden)
+                g2_t = g2.t().contiguous()
+                base = 8 * layer + 4 * d
+                w_grads[base] = gemm_nt(g2_t, x_rows)
+                w_grads[base + 1] = gemm_nt(g2_t, h_prev[d].reshape(rows, hidden).t())
+                w_grads[base + 2] = d_b[d] if lw[4 * d + 2] is not None else None
+                w_grads[base + 3] = d_b[d] if lw[4 * d + 3] is not None else None
+                if need_dx:
+                    part = gemm_nt(g2, lw[4 * d].t())
+                    dx = part if dx is None else dx + part
+            d_h0s[layer], d_c0s[layer] = d_h0, d_c0
+            if need_dx:
+                d_top = dx.reshape(t, n, in_size)
+        return _stack_grads(ctx, d_top, torch.cat(d_h0s, 0), torch.cat(d_c0s, 0), w_grads)
+
+
+def _checked_lens(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx) -> torch.Tensor:
+    """The host lengths of a time-major batch for ``rnn``, after every shape check that needs no device."""
     if x.dim() != 3 or x.shape[2] != rnn.rnn.input_size or min(x.shape) <= 0:
         raise ValueError(f"x must be [T, N, In] with In = {rnn.rnn.input_size}, got {tuple(x.shape)}")
     t, n, _ = x.shape
@@ -227,14 +371,55 @@ def lstm_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple
         raise ValueError("lens must be sorted in decreasing order")
     if int(lens_cpu.min()) < 1 or int(lens_cpu.max()) > t:
         raise ValueError(f"lengths must be in [1, {t}]")
-    nl, hidden = rnn.rnn.num_layers, rnn.rnn.hidden_size
+    states, hidden = rnn.rnn.num_layers * (2 if rnn.bidirectional else 1), rnn.rnn.hidden_size
     if hx is not None:
-        if len(hx) != 2 or any(tuple(s.shape) != (nl, n, hidden) for s in hx):
-            raise ValueError(f"hx must be (h0, c0), each [{nl}, {n}, {hidden}]")
+        if len(hx) != 2 or any(tuple(s.shape) != (states, n, hidden) for s in hx):
+            raise ValueError(f"hx must be (h0, c0), each [{states}, {n}, {hidden}]")
+    return lens_cpu
+
+
+def _stack_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx):
+    """The autograd node of an LSTM stack the caller has vetted: ``_LSTMStackFunction`` or ``_BiLSTMStackFunction``."""
+    lens_cpu = _checked_lens(rnn, x, lens, hx)
     _lib.require_gpu()
     max_len = int(lens_cpu[0])
-    flat = [p for layer in rnn._layer_params() for p in layer[0]]
+    if rnn.bidirectional:
+        node, flat = _BiLSTMStackFunction, [p for layer in rnn._layer_params() for d in layer for p in d]
+    else:
+        node, flat = _LSTMStackFunction, [p for layer in rnn._layer_params() for p in layer[0]]
     h0, c0 = hx if hx is not None else (None, None)
-    out, hn, cn = _LSTMStackFunction.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None,
-                                           x, h0, c0, *flat)
+    out, hn, cn = node.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None, x, h0, c0,
+                             *flat)
     return out, (hn, cn)
+
+
+def rnn_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+              ) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+    """``lstm_train`` for LSTM stacks of either kind: x [T, N, In] TIME-MAJOR (whatever ``rnn.batch_first`` says:
+    ``RNN.forward(differentiable=True)`` does the transposes), lens [N] sorted descending, hx = (h0, c0)
+    [num_layers * ndir, N, H] or None (zeros) -> ``(out [T, N, ndir H], (h_n, c_n))`` with ``RNN.forward``'s values,
+    differentiable in x, hx and every parameter, the ``_reverse`` ones included.  A unidirectional stack is ``lstm_train``'s
+    node; a bidirectional one runs both directions' backward recurrences in the same launches."""
+    if not isinstance(rnn, RNN):
+        raise ValueError(f"rnn_train serves RNN modules, not {type(rnn).__name__} (HardLSTM has no backward in this project)")
+    if rnn.rnn_type != RNNType.LSTM:
+        raise ValueError("rnn_train serves LSTM stacks only (GRU and tanh cells have no backward in this project)")
+    if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
+        raise ValueError("rnn_train does not serve inter-layer dropout in training mode")
+    return _stack_train(rnn, x, lens, hx)
+
+
+def lstm_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+               ) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+    """x [T, N, In] time-major, lens [N] sorted descending, hx = (h0, c0) [num_layers, N, H] or None (zeros) ->
+    ``(out [T, N, H], (h_n, c_n))`` with ``RNN.forward``'s values (rows past a length are 0, the states are those at
+    ``lens[n] - 1``), differentiable in x, hx and every parameter of the stack.  ``RNN.forward`` itself is untouched."""
+    if not isinstance(rnn, RNN) or rnn.rnn_type != RNNType.LSTM:
+        raise ValueError("lstm_train serves LSTM stacks only (GRU and tanh cells have no backward in this project)")
+    if rnn.bidirectional:
+        raise ValueError("lstm_train does not serve bidirectional=True (rnn_train does)")
+    if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
+        raise ValueError("lstm_train does not serve inter-layer dropout in training mode")
+    if rnn.batch_first:
+        raise ValueError("lstm_train takes time-major input (batch_first=False)")
+    return _stack_train(rnn, x, lens, hx)
