@@ -77,7 +77,8 @@ const char* ms_last_error(void);
 /* ---- model/cnn.py ------------------------------------------------------- */
 
 /* MaskConv{1,2}d._mask_ (cnn.py:280-293, 425-443): x[n, :, t] = 0 for t >= lens[n],
- * in place.  x is [N, inner, T]. */
+ * in place.  x is [N, inner, T].  A negative length counts as 0, a length of T or more leaves the utterance alone; the
+ * zeros written are +0.0 whatever the element held (NaN and Inf included), every other element keeps its bits. */
 int ms_mask_time_(float* x, const int32_t* lens, int N, int inner, int T, void* stream);
 
 /* Bytes of the packed filter bank ms_maskconv_pack writes (Cout = all groups). */
@@ -169,7 +170,9 @@ int ms_maskconv1d_gemm_forward(const float* x, const int32_t* lens, const void* 
 /* DeepSpeech2._conv_to_rnn_size (deep_speech_2.py:114-117): [N, CF, T] -> [T, N, CF]. */
 int ms_nct_to_tnc(const float* x, float* y, int N, int CF, int T, void* stream);
 
-/* Elementwise clamp (SeqLenWrapper(Hardtanh/ReLU) on its own); y may alias x. */
+/* Elementwise clamp (SeqLenWrapper(Hardtanh/ReLU) on its own); y may alias x.  min(max(x, lo), hi) for every x that is a
+ * number; a NaN stays a NaN (torch.clamp, F.hardtanh), as in every fused clamp of this library (MS_ACT_CLAMP epilogues, the
+ * hard sigmoid and hard tanh of MS_CELL_HARD_LSTM).  n == 0 is valid and touches no pointer. */
 int ms_clamp(const float* x, float* y, size_t n, float lo, float hi, void* stream);
 
 /* ---- model/fully_connected.py ------------------------------------------ */
@@ -433,7 +436,8 @@ int ms_ctc_loss_backward(const float* logits, const int32_t* in_lens, const int3
 /* CTCGreedyDecoder.forward (ctc_greedy_decoder.py:74-92): argmax over symbols
  * (ties -> lowest index), drop repeats and blanks.  x [T,N,V] (any real scores);
  * out_idx [N, T] int32, out_len [N]; row n's entries past out_len[n] are unspecified (alphabets beyond 64 symbols keep
- * the frames' arg maxes there before the in-place compaction). */
+ * the frames' arg maxes there before the in-place compaction).  lens[n] is clamped to [0, T].  The arg max of a frame: a NaN
+ * counts as the maximum and the first NaN wins (torch.argmax); a frame of all -inf decodes to symbol 0. */
 int ms_ctc_greedy_decode(const float* x, const int32_t* lens, int32_t* out_idx, int32_t* out_len, int T, int N,
                          int V, int blank, void* stream);
 
@@ -669,8 +673,9 @@ int ms_embedding_forward(const float* table, const int32_t* idx, float* out, int
 int ms_rnnt_joint_forward(const float* enc_p, const int32_t* enc_row, const float* pred_p, const float* w_out,
                           const float* b_out, float* logp, int R, int J, int V1, void* stream);
 
-/* Per row b of scores [B, C]: the k largest entries in descending order (ties -> lowest index);
- * -inf entries are never selected (index -1 is written when fewer than k finite candidates exist). */
+/* Per row b of scores [B, C]: the k largest entries in descending order (ties -> lowest index); k may exceed C.
+ * -inf entries are never selected, and neither is a NaN (no comparison with it holds: a row's NaN scores are passed over as
+ * if they were -inf); the places left when fewer than k entries lie above -inf hold (index -1, value -inf). */
 int ms_rnnt_topk(const float* scores, int32_t* out_idx, float* out_val, int B, int C, int k, void* stream);
 
 /* Whole-batch RNN-T decode on the device (own specification, oracle/rnnt_oracle.py): one call enqueues the

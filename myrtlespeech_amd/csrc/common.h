@@ -34,11 +34,13 @@ void set_error(const std::string& s);
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// The clamp activation of the GEMM epilogues (Linear + torch.nn.Hardtanh): min(max(v, lo), hi) for every v that is a number,
-// bit for bit, and NaN for a NaN (fminf / fmaxf return their other argument, which would turn a NaN into `lo`).
+// The clamp activation of every epilogue and of the hard cell (torch.clamp, torch.nn.Hardtanh, np.clip): lo where v < lo, hi
+// where v > hi, v itself otherwise.  Neither comparison holds for a NaN, so a NaN stays a NaN (fminf / fmaxf return their
+// other argument, which would turn it into `lo`), and a zero at a zero limit keeps its sign as it does in torch and numpy
+// (the hardware's max of -0 and +0 is +0).  For every other v this is min(max(v, lo), hi) bit for bit.
 __device__ __forceinline__ float act_clamp(float v, float lo, float hi) {
-  const float c = fminf(fmaxf(v, lo), hi);
-  return v != v ? v : c;
+  const float c = v < lo ? lo : v;
+  return c > hi ? hi : c;
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -108,10 +110,11 @@ constexpr bool prec_half_planes(int P) { return P == PREC_F16X3 || P == PREC_F16
 typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_ __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8_ __attribute__((ext_vector_type(8)));
-// (a saturating conversion: fmed3 turns +-Inf into +-65504 and a NaN into -65504.  The convolution kernels -- the im2col
-// planes of conv1d_gemm.hip included --, the recurrence's h planes and the transducer kernels convert with it; the operands
-// that ms_linear_split_* splits and the x planes of the LSTM input projection, dense (split_planes_kernel) or packed
-// (rnn.hip: split_planes_packed_kernel), go through plane_bits_keep below)
+// (a saturating conversion: fmed3 turns +-Inf into +-65504 and a NaN into -65504.  Every packed weight, the recurrence's h
+// planes and the transducer kernels convert with it; the operands that ms_linear_split_* splits, the x planes of the LSTM
+// input projection, dense (split_planes_kernel) or packed (rnn.hip: split_planes_packed_kernel), the activation planes of
+// every convolution (conv_cl.hip: split_act_by_prec) and the im2col patches of conv1d_gemm.hip go through plane_bits_keep
+// below)
 template <bool HM>
 __device__ __forceinline__ unsigned plane_bits(float x) {
   if constexpr (HM) return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)__builtin_amdgcn_fmed3f(x, -65504.f, 65504.f));

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void maskconv_kernel(const float* __restrict__
       const int co = tile * CO_T + ms::mfma32_row(r, lane);
       if (co < p.Cout_g) {
         float v = acc[r] + (bias ? bias[co] : 0.f);
-        if (p.act == MS_ACT_CLAMP) v = fminf(fmaxf(v, p.lo), p.hi);
+        if (p.act == MS_ACT_CLAMP) v = ms::act_clamp(v, p.lo, p.hi);
         y[(size_t)n * p.y_nstride + ((size_t)co * p.Fout + fo) * p.Tout + t] = v;
       }
     }

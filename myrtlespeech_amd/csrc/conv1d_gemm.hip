@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void conv1d_im2col_kernel(const float* __restr
         if (t >= 0 && t < len) v = xn[(size_t)ci * Tin + t];
       }
       unsigned hb, lb;
-      ms::plane_split<HM>(v, hb, lb);
+      ms::plane_split_keep<HM>(v, hb, lb);   // (a NaN or an Inf stays one: every patch element is a real input or an explicit zero)
       th[tr][cl] = (unsigned short)hb;
       tl[tr][cl] = (unsigned short)lb;
     }

@@ -32,6 +32,7 @@ constexpr int CL_F = 2;    // output feature rows per wave (accumulator tiles)
 struct ClP {
   int N, Cin, Fin, Tin, Cout, Fout, Tout, KF, KT, SF, ST, DF, DT, pad_f, pad_t;
   int KG;        // Cin / 8
+  int KW;        // feature-window mode: the KF rows of a window (its KG granules are KF rounded up to 16 rows); else 0
   int PW;        // staged frames per input row = (frames per workgroup - 1)*ST + (KT-1)*DT + 1
   int co_tiles;
   int act;
@@ -54,6 +55,28 @@ __device__ __forceinline__ void split_by_prec(float x, int prec, unsigned& hi, u
   if (prec == ms::PREC_F16) { hi = f16b(x); lo = 0u; }
   else if (prec == ms::PREC_F16X3) ms::plane_split<true>(x, hi, lo);
   else ms::plane_split<false>(x, hi, lo);
+}
+
+// The same for activations (the layout passes of ms_maskconv_cl_forward and ms_maskconv_fwin_forward, the planes a first
+// convolution hands on): finite values get split_by_prec's bits, NaN and +-Inf stay what they are (ms::plane_bits_keep), so a
+// diverged activation does not come out of the convolution as a number.
+__device__ __forceinline__ void split_act_by_prec(float x, int prec, unsigned& hi, unsigned& lo) {
+  if (prec == ms::PREC_F16) { hi = f16b(x); lo = 0u; }
+  else if (prec == ms::PREC_F16X3) ms::plane_split_keep<true>(x, hi, lo);
+  else ms::plane_split_keep<false>(x, hi, lo);
+}
+
+// Feature-window mode: a window's KF rows are padded to whole 16-row k-steps, and the rows under it -- which belong to the
+// windows of other output rows -- meet the zero filters of conv_fwin_pack_kernel.  0 x NaN is NaN, so those operand elements
+// are cleared where they are read: the mask that keeps the first `keep` of a granule's eight 16-bit elements.
+__device__ __forceinline__ u32x4 granule_mask(int keep) {
+  u32x4 m;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int k = keep - 2 * w;
+    m[w] = k >= 2 ? 0xFFFFFFFFu : (k == 1 ? 0x0000FFFFu : 0u);
+  }
+  return m;
 }
 
 // packed[plane][kf][kt][kg][cout_pad][8] <- w[cout][cin][kf][kt]
@@ -141,6 +164,11 @@ __global__ __launch_bounds__(256, 2) void maskconv_cl_kernel(const unsigned shor
             const int boff = (int)((((size_t)n * p.Tin + tin) * p.FP + (size_t)(fo0 + f) * p.SF + kg * 8) * 2);
             vh = __builtin_amdgcn_raw_buffer_load_b128(xh_rsrc, boff, 0, 0);
             if (!F16) vl = __builtin_amdgcn_raw_buffer_load_b128(xl_rsrc, boff, 0, 0);
+            if (kg * 8 + 8 > p.KW) {            // the rows under this window: another output row's, zero filters here
+              const u32x4 gm = granule_mask(p.KW - kg * 8);
+              vh &= gm;
+              vl &= gm;
+            }
           } else {
             const size_t off = (rbase + tin) * p.Cin + kg * 8;
             vh = *reinterpret_cast<const u32x4*>(xh + off);
@@ -206,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void maskconv_cl_kernel(const unsigned shor
         const int co = tile * 32 + ms::mfma32_row(r, lane);
         if (co < p.Cout) {
           float v = acc[f][r] * winv + (bias ? bias[co] : 0.f);   // (winv: the packed weights' 2^-s, exact)
-          if (p.act == MS_ACT_CLAMP) v = fminf(fmaxf(v, p.lo), p.hi);
+          if (p.act == MS_ACT_CLAMP) v = ms::act_clamp(v, p.lo, p.hi);
           y[(((size_t)n * p.Cout + co) * p.Fout + fo) * p.Tout + t] = v;
         }
       }
@@ -340,7 +368,7 @@ __global__ __launch_bounds__(256, 1) void maskconv_cl_short_kernel(const unsigne
         const int co = cb * 16 + 4 * q + r;
         if (co < p.Cout) {
           float o = v[r] * winv + (bias ? bias[co] : 0.f);
-          if (p.act == MS_ACT_CLAMP) o = fminf(fmaxf(o, p.lo), p.hi);
+          if (p.act == MS_ACT_CLAMP) o = ms::act_clamp(o, p.lo, p.hi);
           y[(((size_t)n * p.Cout + co) * p.Fout + fo) * p.Tout + c16] = o;
         }
       }
@@ -477,6 +505,10 @@ __global__ __launch_bounds__(256, 2) void maskconv_fwin_shared_kernel(const unsi
   int row_off[FS_MR];
 #pragma unroll
   for (int f = 0; f < FS_MR; ++f) row_off[f] = min(rg * FS_MR + f, nrows - 1) * p.RG * gran_bytes;
+  // the rows under a window lie in its last k-step (granules KG - 2, KG - 1): cleared as they are read, since the staged span
+  // is shared and the same element is inside the next output row's window
+  const int s_full = p.KW < p.KG * 8 ? p.KG / 2 - 1 : p.KG / 2;     // k-steps whose 16 rows all lie inside the window
+  const u32x4 gm = granule_mask(p.KW - (p.KG - 2 + half) * 8);
 
   for (int kt0 = 0; kt0 < p.KT; kt0 += FS_TS) {
     const int ntap = min(FS_TS, p.KT - kt0);
@@ -486,7 +518,8 @@ __global__ __launch_bounds__(256, 2) void maskconv_fwin_shared_kernel(const unsi
       // frame (fb*32 + l31)*ST + kt*DT sits in slot [kt*DT % ST][fb*32 + l31 + kt*DT / ST]
       const int kd = (kt0 + ktl) * p.DT, kq = kd / p.ST, kr = kd - kq * p.ST;
       const int lane_off = (kr * p.PQ + kq + fb * 32 + l31) * 16;
-      for (int s = 0; s < p.KG / 2; ++s) {
+      // (the k-steps without rows under the window run the unmasked body: no branch and no mask in their MFMA loop)
+      auto k_step = [&](int s, auto tail) {
         const int kg = 2 * s + half;
         const int woff = ((ktl * p.KG + kg) * 32 + l31) * 16;
         const u32x4 ah = *reinterpret_cast<const u32x4*>(Wh + woff);
@@ -495,17 +528,21 @@ __global__ __launch_bounds__(256, 2) void maskconv_fwin_shared_kernel(const unsi
 #pragma unroll
         for (int f = 0; f < FS_MR; ++f) {
           const int poff = row_off[f] + kg * gran_bytes + lane_off;
-          const u32x4 bh = *reinterpret_cast<const u32x4*>(Ph + poff);
+          u32x4 bh = *reinterpret_cast<const u32x4*>(Ph + poff);
+          if constexpr (decltype(tail)::value) bh &= gm;
           if (F16) {
             acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh), acc[f], 0, 0, 0);
           } else {
-            const u32x4 bl = *reinterpret_cast<const u32x4*>(Pl + poff);
+            u32x4 bl = *reinterpret_cast<const u32x4*>(Pl + poff);
+            if constexpr (decltype(tail)::value) bl &= gm;
             acc[f] = ms::mfma_32x32x16<HM>(ah, bh, acc[f]);
             acc[f] = ms::mfma_32x32x16<HM>(al, bh, acc[f]);
             acc[f] = ms::mfma_32x32x16<HM>(ah, bl, acc[f]);
           }
         }
-      }
+      };
+      for (int s = 0; s < s_full; ++s) k_step(s, std::false_type{});
+      if (s_full < p.KG / 2) k_step(s_full, std::true_type{});
     }
     if (more) {
       __syncthreads();   // this stage's filter reads are done
@@ -533,8 +570,8 @@ __global__ __launch_bounds__(256, 2) void maskconv_fwin_shared_kernel(const unsi
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             float v = acc[f][4 * r4 + e] * winv + (bias ? bias[co + e] : 0.f);
-            if (p.act == MS_ACT_CLAMP) v = fminf(fmaxf(v, p.lo), p.hi);
-            split_by_prec(v, P, h[e], l[e]);
+            if (p.act == MS_ACT_CLAMP) v = ms::act_clamp(v, p.lo, p.hi);
+            split_act_by_prec(v, P, h[e], l[e]);
           }
           const size_t o = (((size_t)n * p.Fout + fo) * p.Tout + t) * p.Cout + co;
           *reinterpret_cast<u32x2*>(oh + o) = u32x2{h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
@@ -547,7 +584,7 @@ __global__ __launch_bounds__(256, 2) void maskconv_fwin_shared_kernel(const unsi
         const int co = tile * 32 + ms::mfma32_row(r, lane);
         if (co < p.Cout) {
           float v = acc[f][r] * winv + (bias ? bias[co] : 0.f);   // (winv: the packed weights' 2^-s, exact)
-          if (p.act == MS_ACT_CLAMP) v = fminf(fmaxf(v, p.lo), p.hi);
+          if (p.act == MS_ACT_CLAMP) v = ms::act_clamp(v, p.lo, p.hi);
           y[(((size_t)n * p.Cout + co) * p.Fout + fo) * p.Tout + t] = v;
         }
       }
@@ -612,7 +649,7 @@ __global__ void nchw_to_cl_split_kernel(const float* __restrict__ x, unsigned sh
       const float v = tile[tx][i];
       const size_t o = (((size_t)n * F + f) * T + t) * C + c;
       unsigned h, l;
-      split_by_prec(v, prec, h, l);
+      split_act_by_prec(v, prec, h, l);
       hi[o] = (unsigned short)h;
       if (prec != ms::PREC_F16) lo[o] = (unsigned short)l;
     }
@@ -637,13 +674,12 @@ __global__ void ft_to_tf_split_kernel(const float* __restrict__ x, unsigned shor
     const int t = t0 + i, j = j0 + tx;
     if (t < T && j < FP) {
       float v = tile[tx][i];
-      // The rows under a window (its KF rows are padded to whole 16-row k-steps) meet the zero filters of
-      // conv_fwin_pack_kernel, and 0 x Inf is NaN in an output that does not read that row: bf16 planes take their operands
-      // clamped to the format's finite range, as plane_bits<true> clamps those of the fp16 planes.
-      if (prec == ms::PREC_BF16X3) v = __builtin_amdgcn_fmed3f(v, -BF16_MAX, BF16_MAX);
+      // bf16 planes take their finite operands clamped to the format's finite range, as plane_bits_keep<true> clamps those of
+      // the fp16 planes; NaN and +-Inf stay (the kernels clear the rows under a window as they read them: granule_mask)
+      if (prec == ms::PREC_BF16X3 && __builtin_fabsf(v) < __builtin_inff()) v = __builtin_amdgcn_fmed3f(v, -BF16_MAX, BF16_MAX);
       const size_t o = ((size_t)n * T + t) * FP + j;
       unsigned h, l;
-      split_by_prec(v, prec, h, l);
+      split_act_by_prec(v, prec, h, l);
       hi[o] = (unsigned short)h;
       if (prec != ms::PREC_F16) lo[o] = (unsigned short)l;
     }
@@ -752,6 +788,7 @@ static ClP fwin_params(int N, int Tin, int Cout, int Fout, int Tout, int KF, int
   ClP p{};
   p.N = N; p.Cin = fwin_kfp(KF); p.Fin = 1; p.Tin = Tin; p.Cout = Cout; p.Fout = Fout; p.Tout = Tout; p.KF = 1; p.KT = KT;
   p.SF = SF; p.ST = ST; p.DF = 1; p.DT = DT; p.pad_f = 0; p.pad_t = pad_t_l; p.KG = p.Cin / 8;
+  p.KW = KF;
   p.co_tiles = ms::cdiv(Cout, 32);
   p.FP = fwin_fp(KF, SF, Fout);
   return p;
@@ -906,6 +943,7 @@ static int cl_forward(const float* x, const int32_t* lens, const void* packed_w,
   p.co_tiles = ms::cdiv(Cout, 32);
   p.act = act; p.lo = act_lo; p.hi = act_hi;
   p.FP = 0;
+  p.KW = 0;
   p.CS = p.RG = p.SG = p.PQ = 0;
   size_t lds = 0;
   const int wf = conv_cl_plan(p, &lds);

@@ -38,7 +38,7 @@ __global__ void nct_to_tnc_kernel(const float* __restrict__ x, float* __restrict
 __global__ void clamp_kernel(const float* x, float* y, size_t n, float lo, float hi) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) y[i] = fminf(fmaxf(x[i], lo), hi);
+  for (; i < n; i += stride) y[i] = ms::act_clamp(x[i], lo, hi);
 }
 
 }  // namespace

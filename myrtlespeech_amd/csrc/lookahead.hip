@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void lookahead_tcontig_kernel(const float* __r
   if (t < To) {
     float acc = 0.f;
     for (int k = 0; k < ctx; ++k) acc += ws[k] * xs[tid + k];
-    if (act == MS_ACT_CLAMP) acc = fminf(fmaxf(acc, lo), hi);
+    if (act == MS_ACT_CLAMP) acc = ms::act_clamp(acc, lo, hi);
     y[n * ys_n + f * ys_f + t * ys_t] = acc;
   }
 }
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void lookahead_strided_kernel(const float* __r
     const int t = t0 + i;
     if (t < To) {
       float v = acc[i];
-      if (act == MS_ACT_CLAMP) v = fminf(fmaxf(v, lo), hi);
+      if (act == MS_ACT_CLAMP) v = ms::act_clamp(v, lo, hi);
       y[n * ys_n + f * ys_f + t * ys_t] = v;
     }
   }

@@ -306,8 +306,8 @@ __device__ __forceinline__ float fast_sigmoid(float v) {
 __device__ __forceinline__ float fast_tanh(float v) {
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008177793f * v));
 }
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
-__device__ __forceinline__ float clamp11(float v) { return fminf(fmaxf(v, -1.f), 1.f); }
+__device__ __forceinline__ float clamp01(float v) { return ms::act_clamp(v, 0.f, 1.f); }
+__device__ __forceinline__ float clamp11(float v) { return ms::act_clamp(v, -1.f, 1.f); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

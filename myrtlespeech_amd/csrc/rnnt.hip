@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ sco
     int bi = 0x7fffffff;
     for (int c = tid; c < C; c += 256) {
       const float v = row[c];
-      if (v > bv || (v == bv && c < bi)) { bv = v; bi = c; }
+      if (v > bv) { bv = v; bi = c; }   // c ascends: the first maximum stays; -inf (and NaN) never beats the start value
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {

@@ -391,6 +391,16 @@ def isolation_cases(entry):
     }[entry]
 
 
+ISOLATION_CLAMP = (-50.0, 120.0)
+
+
+def clamped_isolation_cases(entry):
+    """The isolation cases with the clamp activation in the epilogue (same draw: ``make`` does not look at the activation).
+    The dense outputs spread over thousands around a bias of up to 1000, so the clamp cuts most of them and not all
+    (tests/test_conv_exact_cpu.py checks that)."""
+    return [c._replace(tag=c.tag + "_clamp", act=ISOLATION_CLAMP) for c in isolation_cases(entry)]
+
+
 def isolation_positions(c):
     """[(label, n, ch, f, t)]: single in-length input positions aimed at the ghosts of the kernels."""
     L = eff_lens(c)

@@ -2,7 +2,7 @@
 ABI on pre-filled buffers -- a sentinel in every output element, a guard row of sentinels past the end, packed filters,
 workspaces and planes buffers filled with 0xFF bytes (NaN as floats, NaN as fp16 / bf16 planes) with a guard of their own --
 and the checks that tests/test_conv_exact_gpu.py makes with it.  ``MS_PRECISION`` is read once per process, so
-``python tests/conv_exact_run.py exact|isolation`` runs the split-kernel checks in a process of its own and prints ``ok``."""
+``python tests/conv_exact_run.py exact|isolation|clamped`` runs the split-kernel checks in a process of its own and prints ``ok``."""
 import os
 import sys
 
@@ -252,6 +252,49 @@ def check_position_isolation(lib, c, seen=None):
     assert not failures, (c.entry, c.tag, len(failures), "failures", failures[:8])
 
 
+def check_clamped_position_isolation(lib, c):
+    """Part (b) under the clamp (lo, hi) of a case of ``clamped_isolation_cases``, as torch.clamp defines it.  Per poisoned
+    position the same inputs run without the activation and with it: an output that reads the position is what np.clip makes
+    of the unclamped run's value there (NaN -> NaN, +Inf -> hi, -Inf -> lo; with a NaN poison all of them are NaN), every
+    other output keeps the clamped clean run's bits."""
+    x, w, b = C.make(c, "dense")
+    assert c.act is not None and np.all(w != 0)
+    lo, hi = np.float32(c.act[0]), np.float32(c.act[1])
+    raw_case = c._replace(act=None)
+    failures, lost = [], []
+    for v in variants(c):
+        lib.ms_conv_set_variant(v)
+        try:
+            packed = Packed(lib, c, w)
+            clean = run(lib, c, x, w, b, packed)
+            C.check(c, "dense", clean, (c.tag, "clean"))
+            for label, n, ch, f, t in C.isolation_positions(c):
+                marked = C.reads(c, n, ch, f, t)
+                for poison in C.POISONS + (-np.inf,):
+                    xb = x.copy()
+                    xb[n, ch, f, t] = poison
+                    raw = run(lib, raw_case, xb, w, b, packed)
+                    got = run(lib, c, xb, w, b, packed)
+                    where = (label, (n, ch, f, t), poison, "variant", v)
+                    leak = ~marked & (bits(got) != bits(clean))
+                    if leak.any():
+                        failures.append(where + (int(leak.sum()), "outputs that do not read it changed, first",
+                                                 np.argwhere(leak)[:3].tolist(), got[leak][:3].tolist()))
+                    want = np.clip(raw[marked], lo, hi)
+                    if np.isnan(poison) and not np.isnan(got[marked]).all():
+                        m = got[marked]
+                        lost.append(where + (int((~np.isnan(m)).sum()), "of", int(m.size), "outputs that read the NaN are numbers, "
+                                             "unclamped", raw[marked][~np.isnan(m)][:3].tolist(), "clamped", m[~np.isnan(m)][:3].tolist()))
+                    same = (np.isnan(got[marked]) & np.isnan(want)) | (bits(got[marked]) == bits(want))
+                    if not same.all():
+                        failures.append(where + (int((~same).sum()), "clamped outputs differ from np.clip of the unclamped ones, "
+                                                 "first", got[marked][~same][:3].tolist(), want[~same][:3].tolist()))
+        finally:
+            lib.ms_conv_set_variant(0)
+    assert not failures, (c.entry, c.tag, len(failures), "failures", failures[:8])
+    assert not lost, (c.entry, c.tag, len(lost), "positions whose NaN did not reach the outputs that read it", lost[:4])
+
+
 def run_pair(lib, c1, c2, x, w1, b1, w2, b2):
     """(y2 by the hand-over, y1 and y2 by the two plain calls)."""
     P, S = _lib.ptr, _lib.stream_ptr()
@@ -317,11 +360,24 @@ def split_isolation(lib, seen=None):
             check_position_isolation(lib, c, seen)
 
 
+def split_clamped(lib):
+    """Every case is run; the cases that failed are reported together."""
+    failed = []
+    for entry in SPLIT_ENTRIES:
+        for c in C.clamped_isolation_cases(entry):
+            try:
+                check_clamped_position_isolation(lib, c)
+            except AssertionError as e:
+                failed.append(c.tag)
+                print("clamped isolation failed:", c.tag, str(e)[:400])
+    assert not failed, ("clamped isolation failed on", failed)
+
+
 if __name__ == "__main__":
     the_lib = _lib.load()
     observed = {}
     for job in sys.argv[1:]:
-        {"exact": split_exact, "isolation": lambda l: split_isolation(l, observed)}[job](the_lib)
+        {"exact": split_exact, "isolation": lambda l: split_isolation(l, observed), "clamped": split_clamped}[job](the_lib)
     for key in sorted(observed):
         print("marked outputs", key, sorted(observed[key]))
     print("ok")

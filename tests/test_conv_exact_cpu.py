@@ -235,3 +235,16 @@ def test_reads_marks_exactly_the_outputs_that_an_input_changes(c):
     xb = x.copy()
     xb[n, :, :, C.eff_lens(c)[n]:] += 1
     assert np.array_equal(C.case_reference(c, xb, w, b), base)
+
+
+@pytest.mark.parametrize("c", [c for e in ENTRIES for c in C.clamped_isolation_cases(e)], ids=ident)
+def test_the_isolation_clamp_cuts_some_outputs_and_not_all(c):
+    """The clamped isolation cases share the draw of the unclamped ones; np.clip, which their device check uses as the
+    definition, keeps NaN and maps the infinities to the limits."""
+    plain = [p for p in C.isolation_cases(c.entry) if p.tag + "_clamp" == c.tag][0]
+    assert all(np.array_equal(a, b) for a, b in zip(C.make(c, "dense"), C.make(plain, "dense")))
+    raw, lo, hi = C.want(plain, "dense"), c.act[0], c.act[1]
+    assert (raw < lo).any() and (raw > hi).any() and ((raw > lo) & (raw < hi)).any()
+    assert np.array_equal(C.want(c, "dense"), np.clip(raw, lo, hi))
+    out = np.clip(np.array([np.nan, np.inf, -np.inf], dtype=np.float32), np.float32(lo), np.float32(hi))
+    assert out.dtype == np.float32 and np.isnan(out[0]) and out[1] == hi and out[2] == lo

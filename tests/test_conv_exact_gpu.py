@@ -67,6 +67,18 @@ def test_a_non_finite_input_reaches_only_the_outputs_that_read_it(lib, c):
     R.check_position_isolation(lib, c)
 
 
+ISO_CLAMPED = [c for e in ("tap",) + R.SPLIT_ENTRIES for c in C.clamped_isolation_cases(e)]
+
+
+@pytest.mark.parametrize("c", ISO_CLAMPED, ids=ident)
+def test_a_non_finite_input_survives_the_clamp_of_the_epilogue(lib, c):
+    """One NaN, +Inf or -Inf at an input position, under the clamp: the outputs that read a NaN are NaN; the outputs that read
+    an Inf are np.clip of the unclamped run's values; every other output keeps the clamped clean run's bits.  On every route:
+    the float32 tap kernel, the channels-last kernels, the im2col GEMM and the feature-window kernels, whose windows are
+    padded with rows that belong to other outputs (cleared where they are read, csrc/conv_cl.hip granule_mask)."""
+    R.check_clamped_position_isolation(lib, c)
+
+
 def test_non_finite_padding_changes_no_output_of_the_handover(lib):
     c1, c2 = C.handover_pairs()[1]
     x, w1, b1, w2, b2 = C.make_pair(c1, c2, "dense")
@@ -87,6 +99,11 @@ def child(precision, jobs):
 
 def test_split_kernels_exact_and_isolated_with_bf16_planes():
     child("bf16x3", ["exact", "isolation"])
+
+
+def test_split_kernels_keep_a_non_finite_input_through_the_clamp_with_bf16_planes():
+    """The same in a process with bf16 planes; the child runs every case and reports those that failed."""
+    child("bf16x3", ["clamped"])
 
 
 def test_split_kernels_exact_with_one_fp16_plane():

@@ -144,3 +144,42 @@ def test_a_non_finite_frame_reaches_the_outputs_that_read_it_and_no_other(lib, k
                 assert not np.isfinite(got[reads]).any(), (what, "an output that reads the frame is finite")
                 bad = ~reads & ~(got == finite)
                 assert not bad.any(), (what, "outputs that do not read the frame changed", np.argwhere(bad)[:6].tolist())
+
+
+@pytest.mark.parametrize("kind", ["tcontig", "fcontig"])
+@pytest.mark.parametrize("ctx", C.ISOLATION_CTX)
+def test_a_non_finite_frame_survives_the_clamp(lib, kind, ctx):
+    """The same poisoned frame under the clamp (lo, hi), as torch.clamp and F.hardtanh define it: an output that reads a NaN
+    is NaN, not ``lo``; an output that reads an Inf is what np.clip makes of the unclamped run's value there (NaN -> NaN,
+    +Inf -> hi, -Inf -> lo); every other output keeps the clamped finite run's bits."""
+    N, F, T = 2, 5, 70
+    act = C.ACTS[1]
+    lo, hi = np.float32(act[0]), np.float32(act[1])
+    x, w = C.make("gauss", N, F, T, ctx)
+    assert np.all(w != 0)
+    wd = torch.from_numpy(w).cuda()
+    n0, f0 = 1, 2
+    for layout in C.LAYOUTS:
+        xv, xs = put(x, kind)
+        finite = lookahead(lib, xv, xs, wd, N, F, T, T, ctx, layout, act, False, (kind, ctx, layout, "finite, clamped"))
+        C.check("gauss", finite, x, w, T, act, (kind, ctx, layout, "finite, clamped"))
+        for t0 in (40, 5, T - 1):
+            for value in (np.inf, -np.inf, np.nan):
+                xb = x.copy()
+                xb[n0, f0, t0] = value
+                xv, xs = put(xb, kind)
+                what = (kind, ctx, layout, t0, value)
+                raw = lookahead(lib, xv, xs, wd, N, F, T, T, ctx, layout, None, False, what + ("unclamped",))
+                got = lookahead(lib, xv, xs, wd, N, F, T, T, ctx, layout, act, False, what + ("clamped",))
+                reads = np.zeros((N, F, T), dtype=bool)
+                reads[n0, f0, max(0, t0 - ctx + 1):t0 + 1] = True
+                assert not np.isfinite(raw[reads]).any(), (what, "an unclamped output that reads the frame is finite")
+                want = np.clip(raw[reads], lo, hi)
+                assert want.dtype == np.float32
+                if np.isnan(value):
+                    assert np.isnan(want).all()
+                same = (np.isnan(got[reads]) & np.isnan(want)) | (got[reads].view(np.uint32) == want.view(np.uint32))
+                assert same.all(), (what, "the clamp did not keep what np.clip keeps", got[reads][~same][:6].tolist(),
+                                    want[~same][:6].tolist())
+                bad = ~reads & ~(got.view(np.uint32) == finite.view(np.uint32))
+                assert not bad.any(), (what, "outputs that do not read the frame changed", np.argwhere(bad)[:6].tolist())
