@@ -624,8 +624,11 @@ int ms_ctc_beam_decode_ex(const float* probs, const int32_t* lens, int32_t* out_
  * 10*log10(max(.,1e-10)) floored at (per-utterance max - top_db) -> dct [n_mfcc, n_mels].
  * wave [N, max_samples] zero-padded, wave_lens [N] (each > n_fft/2); dft [2*(n_fft/2+1), n_fft] holds
  * the cos rows then the -sin rows.  out [N, n_mfcc, T], T = 1 + max_samples/hop; utterance n has
- * 1 + wave_lens[n]/hop frames, later frames are zero (what data/batch.py:7-42 pads with).
- * top_db < 0 disables the floor. */
+ * 1 + wave_lens[n]/hop frames, later frames are zero (what data/batch.py:7-42 pads with); a
+ * wave_lens[n] above max_samples counts as max_samples.  top_db < 0 disables the floor.
+ * The dB step and its floor select like torch.clamp and torch.max, so a NaN, an Inf or an overflowing
+ * sample makes every feature of its own utterance NaN (as in torchaudio) and touches no other utterance.
+ * MS_ERR_WORKSPACE for a workspace below ms_mfcc_workspace_bytes. */
 size_t ms_mfcc_workspace_bytes(int N, int T, int n_fft, int n_mels, int n_mfcc);
 int ms_mfcc_forward(const float* wave, const int32_t* wave_lens, const float* window, const float* dft,
                     const float* mel_fb, const float* dct, float* out, int N, int max_samples, int T, int n_fft,
@@ -638,7 +641,7 @@ int ms_mfcc_forward(const float* wave, const int32_t* wave_lens, const float* wi
  * frame_step samples (zero-padded tail), |DFT_nfft|^2/nfft, fbank [nfilt, nfft/2+1], log,
  * dct [numcep, nfilt], lifter [numcep], coefficient 0 := log(frame energy).  twiddle [nfft, 2] holds
  * (cos, sin)(2 pi j / nfft).  out [N, numcep, T] float32, T = frame count of max_samples; frames
- * past an utterance's own count are zero. */
+ * past an utterance's own count are zero; a wave_lens[n] above max_samples counts as max_samples. */
 int ms_mfcc_legacy_forward(const float* wave, const int32_t* wave_lens, const double* twiddle, const double* fbank,
                            const double* dct, const double* lifter, float* out, int N, int max_samples, int T,
                            int frame_len, int frame_step, int nfft, int nfilt, int numcep, double preemph,
@@ -646,7 +649,8 @@ int ms_mfcc_legacy_forward(const float* wave, const int32_t* wave_lens, const do
 
 /* Standardize.__call__ (data/preprocess.py:57-63) per utterance: y = (x - mean) / std (unbiased)
  * over x[n, :, t < lens[n]]; x, y [N, inner, T]; frames t >= lens[n] are written as 0.  lens may be
- * NULL (every utterance is T frames long).  y may alias x. */
+ * NULL (every utterance is T frames long).  y may alias x.  MS_ERR_WORKSPACE for a workspace below
+ * ms_standardize_workspace_bytes. */
 size_t ms_standardize_workspace_bytes(int N);
 int ms_standardize_forward(const float* x, const int32_t* lens, float* y, int N, int inner, int T, void* workspace,
                            size_t workspace_bytes, void* stream);

@@ -15,8 +15,10 @@ namespace {
 
 __device__ __forceinline__ int frames_of(int samples, int hop) { return 1 + samples / hop; }
 
-// Monotonic float <-> int key so a float maximum can be an integer atomicMax.
+// Monotonic float <-> int key so a float maximum can be an integer atomicMax.  A NaN of either sign takes the largest key
+// (key_float gives a NaN back for it), so it wins the maximum as it does in torch.max and np.max.
 __device__ __forceinline__ int float_key(float f) {
+  if (f != f) return INT_MAX;
   const int b = __float_as_int(f);
   return b >= 0 ? b : b ^ 0x7fffffff;
 }
@@ -28,7 +30,7 @@ __global__ void stft_frames_kernel(const float* __restrict__ wave, const int32_t
                                    const float* __restrict__ window, float* __restrict__ frames, int max_samples, int T,
                                    int n_fft, int hop) {
   const int n = blockIdx.y, t = blockIdx.x;
-  const int len = wave_lens[n];
+  const int len = min(wave_lens[n], max_samples);   // the row holds max_samples samples whatever the caller claims
   float* dst = frames + ((size_t)n * T + t) * n_fft;
   const bool live = len > 0 && t < frames_of(len, hop);
   const float* src = wave + (size_t)n * max_samples;
@@ -62,11 +64,13 @@ __global__ void to_db_kernel(float* __restrict__ mel, const int32_t* __restrict_
                              int T, int n_mels, int hop, float multiplier, float amin, float db_offset) {
   __shared__ int red[4];
   const int n = blockIdx.y;
-  const int valid = frames_of(wave_lens[n], hop) * n_mels;   // valid prefix of this utterance's [T, n_mels] block
+  const int valid = min(frames_of(wave_lens[n], hop), T) * n_mels;   // valid prefix of this utterance's [T, n_mels] block
   float* base = mel + (size_t)n * T * n_mels;
   int best = INT_MIN;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < T * n_mels; i += gridDim.x * blockDim.x) {
-    const float v = multiplier * log10f(fmaxf(base[i], amin)) - db_offset;
+    const float p = base[i];
+    // torch.clamp(min=amin): a select, since fmaxf(NaN, amin) is amin and a poisoned frame would come out as silence
+    const float v = multiplier * log10f(p < amin ? amin : p) - db_offset;
     base[i] = v;
     if (i < valid) best = max(best, float_key(v));
   }
@@ -84,8 +88,12 @@ __global__ void db_floor_kernel(float* __restrict__ mel, const int* __restrict__
   const int n = blockIdx.y;
   const float floor_db = key_float(maxkey[n]) - top_db;
   float* base = mel + (size_t)n * T * n_mels;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < T * n_mels; i += gridDim.x * blockDim.x)
-    base[i] = fmaxf(base[i], floor_db);
+  // torch.max(x, floor): v where v > floor or v is NaN, else the floor -- which is NaN when the maximum was, and then every
+  // comparison fails and the whole utterance is NaN, as it is in torchaudio.  fmaxf drops a NaN on either side.
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < T * n_mels; i += gridDim.x * blockDim.x) {
+    const float v = base[i];
+    base[i] = (v > floor_db || v != v) ? v : floor_db;
+  }
 }
 
 // cep [N*T, C] -> out [N, C, T], zero for t >= frames(n).  32x32 LDS tile transpose.
@@ -214,7 +222,7 @@ __global__ void __launch_bounds__(256) mfcc_legacy_kernel(
   double* feat = pspec + nbins;           // [nfilt]
   double* red = feat + nfilt;             // [4]
   const int n = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-  const int slen = wave_lens[n];
+  const int slen = min(wave_lens[n], max_samples);   // the row holds max_samples samples whatever the caller claims
   if (t >= legacy_frames(slen, frame_len, frame_step)) {
     for (int c = tid; c < numcep; c += blockDim.x) out[((size_t)n * numcep + c) * T + t] = 0.0f;
     return;
@@ -307,7 +315,10 @@ extern "C" int ms_mfcc_forward(const float* wave, const int32_t* wave_lens, cons
   MS_REQUIRE(T == 1 + max_samples / hop, "T must be 1 + max_samples / hop");
   MS_REQUIRE(N <= 65535 && T <= 2147483647 / N, "N/T exceed grid limits");
   const MfccLayout L(N, T, n_fft, n_mels, n_mfcc);
-  MS_REQUIRE(workspace_bytes >= L.total, "workspace too small");
+  if (workspace_bytes < L.total) {
+    ms::set_error("ms_mfcc_forward: workspace too small");
+    return MS_ERR_WORKSPACE;
+  }
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   float* frames = (float*)(ws + L.frames);
@@ -352,7 +363,10 @@ extern "C" int ms_standardize_forward(const float* x, const int32_t* lens, float
   MS_REQUIRE(x && y && workspace, "null pointer");
   MS_REQUIRE(N > 0 && inner > 0 && T > 0, "bad shape");
   MS_REQUIRE(N <= 65535, "N exceeds grid limits");
-  MS_REQUIRE(workspace_bytes >= (size_t)N * 16, "workspace too small");
+  if (workspace_bytes < (size_t)N * 16) {
+    ms::set_error("ms_standardize_forward: workspace too small");
+    return MS_ERR_WORKSPACE;
+  }
   hipStream_t s = (hipStream_t)stream;
   double* stats = (double*)workspace;
   MS_HIP(hipMemsetAsync(stats, 0, (size_t)N * 16, s));
