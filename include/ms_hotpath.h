@@ -1037,6 +1037,50 @@ int ms_lstm_backward_steps_bidir(const float* gates, const float* c, const float
                                  int N, int H, void* stream);
 int ms_embedding_backward(const float* d_out, const int32_t* idx, float* d_table, int R, int D, int V1, void* stream);
 
+/* ---- training: convolution and lookahead backward (csrc/conv_backward.hip) -- OWN specification ---------------------
+ *
+ * The forward is ms_maskconv_forward's contract with groups == 1:
+ *   y = act(b[co] + sum_{ci,kf,kt} w[co,ci,kf,kt] xm[n, ci, fo SF - pad_f + kf DF, to ST - pad_t + kt DT])
+ * where xm is x with frames t >= min(lens[n], Tin) read as 0 and everything outside [0, Fin) x [0, Tin) read as 0.  w is
+ * torch's [Cout, Cin, KF, KT] (no packed bank), x [N, Cin, Fin, Tin], y and dy [N, Cout, Fout, Tout], lens [N] or NULL.
+ *
+ * Gate: g = dy where act == MS_ACT_NONE or act_lo < y < act_hi strictly, +0 elsewhere: the saved OUTPUT decides, no
+ * pre-activation is kept (y may be NULL when act == MS_ACT_NONE).
+ *
+ * ms_maskconv_backward_data:   dx[n,ci,fi,ti] = sum w[co,ci,kf,kt] g[n,co,fo,to] over every (co,kf,kt,fo,to) with
+ *   fi = fo SF - pad_f + kf DF, ti = to ST - pad_t + kt DT, 0 <= fo < Fout, 0 <= to < Tout.  dx[n,:,:,t] = +0.0 for
+ *   t >= lens[n] (a select: whatever g holds), and an input position that no window reads gets +0.0.  dx is fully written.
+ * ms_maskconv_backward_weight: dw[co,ci,kf,kt] = sum_{n,fo,to} g[n,co,fo,to] xm[...] over in-range positions,
+ *   db[co] = sum_{n,fo,to} g (db may be NULL).  A masked or padded position is a load predicate, never a product with what
+ *   memory holds there.  The reduction over K = N Fout Tout is cut into ceil(K / 8192) slices -- a function of the arguments
+ *   only -- whose partials [slices][Cout][Cin KF KT + 1] go to the workspace (ms_maskconv_backward_workspace_bytes) and are
+ *   added in ascending slice order by a second launch.
+ *
+ * Arithmetic: v_mfma_f32_32x32x2_f32, float32 accumulation, no atomics: the same bits on every run and every device.  One
+ * route per gradient serves every geometry (the file's header comment): the data gradient tiles 32 input channels x 128
+ * frames of one time-stride residue class, the weight gradient 32 output channels x 128 flattened (ci,kf,kt) columns.
+ *
+ * Errors: NULL operands and bad geometry (a non-positive extent, stride or dilation, a negative pad, an unknown act, an
+ * output row or frame that starts past the input) MS_ERR_INVALID with nothing launched; a short workspace MS_ERR_WORKSPACE.
+ * Out of scope: groups > 1.
+ *
+ * ms_lookahead_backward: forward z[n,f,t] = sum_{k<ctx} w[f,k] x[n,f,t+k] (zero beyond T), y = act(z); with the same gate
+ *   dx[n,f,t] = sum_{k <= min(t, ctx-1)} w[f,k] g[n,f,t-k]   and   dw[f,k] = sum_n sum_{t: t+k<T} g[n,f,t] x[n,f,t+k]
+ * (n, then t, ascending).  x / dx share the element strides xs_*, y / dy the strides ys_*, as in ms_lookahead_forward; w and
+ * dw are [F, ctx].  Taps are guarded by k < ctx and t + k < T, never padded with zero weights.  dx or dw may be NULL (that
+ * gradient is not wanted; x may then be NULL with dw). */
+size_t ms_maskconv_backward_workspace_bytes(int N, int Cin, int Cout, int Fout, int Tout, int KF, int KT);
+int ms_maskconv_backward_data(const float* w, const float* y, const float* dy, const int32_t* lens, float* dx, int N, int Cin,
+                              int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST, int DF, int DT,
+                              int pad_f_l, int pad_t_l, int act, float act_lo, float act_hi, void* stream);
+int ms_maskconv_backward_weight(const float* x, const float* y, const float* dy, const int32_t* lens, float* dw, float* db,
+                                int N, int Cin, int Fin, int Tin, int Cout, int Fout, int Tout, int KF, int KT, int SF, int ST,
+                                int DF, int DT, int pad_f_l, int pad_t_l, int act, float act_lo, float act_hi, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int ms_lookahead_backward(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw, int N, int F,
+                          int T, int ctx, long xs_n, long xs_f, long xs_t, long ys_n, long ys_f, long ys_t, int act,
+                          float act_lo, float act_hi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,10 @@ SIGNATURES = {
     "ms_lstm_recompute_dir": (c_int, [_P] * 11 + [c_int] * 5 + [_P, c_size_t, _P]),
     "ms_lstm_backward_steps_bidir": (c_int, [_P] * 9 + [c_int] + [_P] * 4 + [c_int] * 3 + [_P]),
     "ms_embedding_backward": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "ms_maskconv_backward_workspace_bytes": (c_size_t, [c_int] * 7),
+    "ms_maskconv_backward_data": (c_int, [_P] * 5 + [c_int] * 16 + [c_float, c_float, _P]),
+    "ms_maskconv_backward_weight": (c_int, [_P] * 6 + [c_int] * 16 + [c_float, c_float, _P, c_size_t, _P]),
+    "ms_lookahead_backward": (c_int, [_P] * 6 + [c_int] * 4 + [c_long] * 6 + [c_int, c_float, c_float, _P]),
     "ms_mfcc_workspace_bytes": (c_size_t, [c_int] * 5),
     "ms_mfcc_forward": (c_int, [_P] * 7 + [c_int] * 7 + [c_float, _P, c_size_t, _P]),
     "ms_mfcc_legacy_forward": (c_int, [_P] * 7 + [c_int] * 8 + [c_double, _P]),

@@ -98,9 +98,88 @@ class DeepSpeech2(torch.nn.Module):
         return lookahead_apply(h_tnf, mods[0].weight, (f, 1, n * f), n, f, t, out_layout="ntf", clamp=clamp)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: Tuple[torch.Tensor, torch.Tensor], hx: Optional[RNNState] = None
+    def forward(self, x: Tuple[torch.Tensor, torch.Tensor], hx: Optional[RNNState] = None, differentiable: bool = False
                 ) -> Tuple[Tuple[torch.Tensor, torch.Tensor], RNNState]:
+        """``differentiable=True``: the same chain as autograd nodes on the device (``model/conv_autograd.py``,
+        ``model/rnn_autograd.py``), so ``CTCLoss()((out, lens), (y, y_lens)).backward()`` fills the gradient of every parameter
+        and of ``hx``; the input features are data and get none.  ValueError, before a device is needed, for what has no
+        backward here: GRU / tanh / ``HardLSTM`` stacks, dropout in training mode, ``groups > 1``, and a ``cnn`` or
+        ``lookahead`` holding modules other than the builder's own.  The default path is untouched."""
+        if differentiable:
+            return self._forward_train(x, hx)
         return self.back(self.front(x), hx)
+
+    def _train_plan(self):
+        """The differentiable chain, vetted without a device: ([(conv, clamp) | view module, ...], (Lookahead, clamp) | None)."""
+        from myrtlespeech_amd.model.rnn import RNN, RNNType
+        what = "DeepSpeech2.forward(differentiable=True)"
+        rnn, fc = self.rnn, self.fully_connected
+        if not isinstance(rnn, RNN) or rnn.rnn_type != RNNType.LSTM:
+            raise ValueError(f"{what} serves LSTM stacks only (GRU and tanh cells and HardLSTM have no backward in this project)")
+        if rnn.batch_first:
+            raise ValueError(f"{what} takes a time-major recurrent stack (batch_first=False), as the builder makes it")
+        if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
+            raise ValueError(f"{what} does not serve inter-layer dropout in training mode")
+        if not isinstance(fc, FullyConnected):
+            raise ValueError(f"{what} serves the builder's FullyConnected, not {type(fc).__name__}")
+        fc_mods = [fc.fully_connected] if isinstance(fc.fully_connected, torch.nn.Linear) else list(fc.fully_connected)
+        if fc.training and any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in fc_mods):
+            raise ValueError(f"{what} does not serve dropout masks: train in .eval() or with dropout = 0")
+        front = []
+        mods = [] if self.cnn is None else (list(self.cnn) if isinstance(self.cnn, torch.nn.Sequential) else [self.cnn])
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, (MaskConv1d, MaskConv2d)):
+                if m.groups != 1:
+                    raise ValueError(f"{what} does not serve convolutions with groups != 1")
+                fused = i + 1 < len(mods) and _is_plain_activation(mods[i + 1])
+                front.append((m, activation_clamp(mods[i + 1].module) if fused else None))
+                i += 2 if fused else 1
+            elif _is_plain_activation(m) and isinstance(m.module, torch.nn.Identity):
+                i += 1
+            elif isinstance(m, (Conv1dTo2d, Conv2dTo1d)) and m.seq_len_support:
+                front.append(m)
+                i += 1
+            else:
+                raise ValueError(f"{what} serves a cnn of MaskConv1d / MaskConv2d, each optionally followed by SeqLenWrapper of "
+                                 f"Hardtanh / ReLU / Identity, Conv1dTo2d and Conv2dTo1d; found {type(m).__name__} at {i}")
+        la = None
+        if self.lookahead is not None:
+            lmods = list(self.lookahead) if isinstance(self.lookahead, torch.nn.Sequential) else [self.lookahead]
+            if not (1 <= len(lmods) <= 2 and isinstance(lmods[0], Lookahead) and all(_is_plain_activation(m) for m in lmods[1:])):
+                raise ValueError(f"{what} serves a lookahead of Lookahead or Sequential(Lookahead, SeqLenWrapper(activation))")
+            la = (lmods[0], activation_clamp(lmods[1].module) if len(lmods) == 2 else None)
+        return front, la
+
+    def _forward_train(self, x: Tuple[torch.Tensor, torch.Tensor], hx: Optional[RNNState]):
+        """``forward`` as a chain of autograd nodes: one node per convolution with its clamp fused (no planes hand-over pair),
+        the (N,C,F,T) -> (T,N,C*F) re-layout as torch ops autograd sees, ``rnn_train``, ``lookahead_train`` and
+        ``linear_stack_train``."""
+        from myrtlespeech_amd.model.conv_autograd import lookahead_train, maskconv_train
+        from myrtlespeech_amd.model.rnn_autograd import linear_stack_train
+        front, la = self._train_plan()
+        acts, lens = x
+        if acts.dim() not in (3, 4) or min(acts.shape) <= 0:
+            raise ValueError(f"the input must be [batch, channels, features, seq_len], got {tuple(acts.shape)}")
+        _lib.require_gpu()
+        h = (_lib.f32c(acts.detach()), lens)
+        for step in front:
+            h = maskconv_train(step[0], h, step[1]) if isinstance(step, tuple) else step(h)
+        seq, lens = h
+        if seq.dim() != 4:
+            raise ValueError(f"the cnn must end on [batch, channels, features, seq_len], got {tuple(seq.shape)}")
+        n, c, f, t = seq.shape
+        seq = seq.reshape(n, c * f, t).permute(2, 0, 1).contiguous()
+        (seq, lens), hid = self.rnn((seq, lens), hx, differentiable=True)
+        t, n, f = seq.shape
+        fc = self.fully_connected
+        if la is not None:
+            ntf = lookahead_train(la[0], seq.contiguous(), la[1])
+            out = linear_stack_train(ntf.reshape(n * t, f), fc.fully_connected, fc.training).reshape(n, t, -1).transpose(0, 1)
+        else:
+            out = linear_stack_train(seq.reshape(t * n, f), fc.fully_connected, fc.training).reshape(t, n, -1)
+        return (out, _lib.lens_to_device(lens)), hid
 
     def front(self, x: Tuple[torch.Tensor, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
         """The part of ``forward`` that depends on the input only: convolutions and the (N,C,F,T) -> (T,N,C*F) re-layout

@@ -20,10 +20,13 @@ direction; tests/bilstm_backward_ref.py restates it.  ``RNN.forward(..., differe
 ``DeepSpeech1.forward(..., differentiable=True)`` are built on it, the latter with ``linear_clamp_train``: a linear layer with
 its ``Hardtanh`` fused, whose backward passes dy where the saved OUTPUT is strictly inside the clamp.
 
+``linear_stack_train`` runs a whole Linear / activation chain (``linear_stack_plan``'s list) through those two nodes.  The masked
+convolutions and the lookahead have their nodes in ``model/conv_autograd.py`` (``maskconv_train``, ``lookahead_train``), and
+``DeepSpeech2.forward(..., differentiable=True)`` strings all of them together.
+
 Out of scope, and refused with ValueError before a device is needed: GRU and tanh cells, ``HardLSTM``, inter-layer dropout
-in training mode (``lstm_train`` also refuses ``bidirectional=True``: ``rnn_train`` serves it).  There is no backward for the
-convolutions, the lookahead or DS2, no dropout mask, no single-launch (persistent) backward recurrence and no mixed-precision
-gradient.
+in training mode (``lstm_train`` also refuses ``bidirectional=True``: ``rnn_train`` serves it), convolutions with
+``groups > 1``.  There is no dropout mask, no single-launch (persistent) backward recurrence and no mixed-precision gradient.
 """
 from typing import Optional, Tuple
 
@@ -153,6 +156,23 @@ def linear_clamp_train(x2d: torch.Tensor, lin: torch.nn.Linear, lo: float, hi: f
     if not lo < hi:
         raise ValueError(f"linear_clamp_train needs lo < hi, got [{lo}, {hi}]")
     return _LinearClampFunction.apply(x2d, lin.weight, lin.bias, lo, hi)
+
+
+def linear_stack_train(x2d: torch.Tensor, stack, training: bool = False) -> torch.Tensor:
+    """``run_linear_stack`` as a chain of autograd nodes: ``stack`` is ``linear_stack_plan``'s list, or the Linear / activation /
+    Dropout chain itself (then ``training`` is the owning module's mode).  A layer with a clamp is ``linear_clamp_train``
+    (``ReLU`` is the clamp (0, +inf)), one without ``linear_train``.  ValueError, before a device is needed, for
+    ``Dropout(p > 0)`` in training mode: there is no dropout mask in this project (DeepSpeech1's rule)."""
+    if isinstance(stack, torch.nn.Module):
+        from myrtlespeech_amd.model.fully_connected import linear_stack_plan
+        mods = [stack] if isinstance(stack, torch.nn.Linear) else list(stack)
+        if training and any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in mods):
+            raise ValueError("linear_stack_train does not serve dropout masks: train in .eval() or with dropout = 0")
+        stack = linear_stack_plan(stack, training)
+    h = x2d
+    for lin, clamp in stack:
+        h = linear_train(h, lin) if clamp is None else linear_clamp_train(h, lin, clamp[0], clamp[1])
+    return h
 
 
 def embedding_train(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
