@@ -390,9 +390,10 @@ size_t ms_ctc_loss_workspace_bytes(int T, int N, int V, int S_max);
  * to wave through an LDS mailbox with a bounded (0.5 s) spin; should an entry never arrive -- it cannot while every wave of
  * the workgroup runs -- the utterance's loss (and its gradient) is NaN AND the word is set.  ms_ctc_status synchronises
  * `stream`, returns MS_ERR_TIMEOUT once if the word was set and clears it (the CTC twin of ms_rnn_status; ctc_loss.py has
- * no such state: torch's kernel cannot time out).  A NaN loss WITHOUT the status is data: a frame whose log-softmax
- * normaliser is not finite (a NaN or +inf logit, a row of -inf) gives NaN as torch.nn.CTCLoss does, also under
- * zero_infinity. */
+ * no such state: torch's kernel cannot time out).  A NaN loss WITHOUT the status is data: a frame (t < in_lens[n]) whose
+ * log-softmax normaliser is not finite (a NaN or +inf logit, a row of -inf) or, under MS_CTC_LOG_PROBS_IN, a NaN among its
+ * values gives NaN as torch.nn.CTCLoss does, also under zero_infinity and whichever kernel runs; ms_ctc_loss_backward
+ * then writes NaN to every element of that utterance's existing frames and zeros behind them. */
 int ms_ctc_status(const void* workspace, void* stream);
 
 /* CTCLoss.forward (ctc_loss.py:95-101) = LogSoftmax(dim=-1) + torch.nn.CTCLoss:

@@ -48,20 +48,36 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_alpha_kernel(const float* __r
   float* logz = logz_ws + (size_t)n * T;
   const int32_t* tg = targets + tgt_offsets[n];
 
+  // a frame whose normaliser is not finite (a NaN / +inf logit, a row of -inf) or, with log-probabilities given, a NaN value:
+  // the loss is NaN whatever zero_infinity says, as in the pipeline kernel (lse3 would turn the NaN into -inf two frames on,
+  // i.e. into a loss of +inf that zero_infinity replaces by 0).  The threads' findings meet in alpha1[0], which the recursion
+  // does not touch before the second barrier below (the dynamic LDS is the whole 160 KiB at the longest target: no static word,
+  // which __syncthreads_or would bring)
+  int bad = 0;
+  if (tid == 0) alpha1[0] = 0.f;
+  __syncthreads();
   for (int t = tid; t < Tn; t += CTC_THREADS) {
-    if (log_probs_in) { logz[t] = 0.f; continue; }   // the caller normalised over another axis (CTCLoss(dim != -1))
     const float* row = logits + ((size_t)t * N + n) * V;
+    if (log_probs_in) {                              // the caller normalised over another axis (CTCLoss(dim != -1))
+      for (int v = 0; v < V; ++v) bad |= (row[v] != row[v]) ? 1 : 0;
+      logz[t] = 0.f;
+      continue;
+    }
     float m = neg_inf();
     for (int v = 0; v < V; ++v) m = fmaxf(m, row[v]);
     float sum = 0.f;
     for (int v = 0; v < V; ++v) sum += expf(row[v] - m);
-    logz[t] = logf(sum) + m;
+    const float lz = logf(sum) + m;
+    bad |= (fabsf(lz) < INFINITY) ? 0 : 1;
+    logz[t] = lz;
   }
   for (int s = tid; s < S; s += CTC_THREADS) {
     ext[s] = (s & 1) ? tg[s >> 1] : blank;
     alpha0[s] = neg_inf();
   }
+  if (bad) alpha1[0] = 1.f;
   __syncthreads();
+  const bool poisoned = alpha1[0] != 0.f;
   if (Tn > 0) {
     const float* row = logits + (size_t)n * V;
     if (tid == 0) alpha0[0] = row[blank] - logz[0];
@@ -121,7 +137,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_alpha_kernel(const float* __r
       const float m = fmaxf(l1, l2);
       ll = (m == neg_inf()) ? neg_inf() : logf(expf(l1 - m) + expf(l2 - m)) + m;
     }
-    nll[n] = -ll;
+    nll[n] = poisoned ? __uint_as_float(0x7fc00000u) : -ll;
   }
 }
 
@@ -387,8 +403,9 @@ __device__ __forceinline__ bool alpha_wave_normalise(const float* __restrict__ l
 
 // One frame of phase 1 for a wide alphabet, by ONE WAVE (lanes across the symbols): the row's normaliser, the per-state copy
 // lps_row[s] of the normalised log2-domain log-probabilities the recursion reads and (ROWS) every symbol's value lpn_row[v] for
-// the gradient kernel.  Returns 1 when the normaliser is not finite.  Called by the pipeline kernel's own four waves (phase 1
-// inside the launch) and by ctc_normalise_wide_kernel (phase 1 as a chip-wide launch of its own).
+// the gradient kernel.  Returns 1 when the normaliser is not finite (in every lane) or, in the lanes that hold one, when a given
+// log-probability is NaN.  Called by the pipeline kernel's own four waves (phase 1 inside the launch) and by
+// ctc_normalise_wide_kernel (phase 1 as a chip-wide launch of its own).
 template <bool ROWS>
 __device__ __forceinline__ int ctc_normalise_wide_frame(const float* __restrict__ row, float* __restrict__ lpn_row,
                                                         float* __restrict__ lps_row, const int32_t* __restrict__ tg, int S, int V,
@@ -426,6 +443,15 @@ __device__ __forceinline__ int ctc_normalise_wide_frame(const float* __restrict_
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     lz = logf(sum) + m;
     bad |= (fabsf(lz) < INFINITY) ? 0 : 1;
+  } else {
+    // given log-probabilities: a NaN among them poisons the utterance, as in alpha_wave_normalise (the clamp below would read
+    // it as "impossible").  Integer arithmetic on the bits (|x| above the bit pattern of infinity carries into bit 31), not a
+    // compare: this runs inside the pipeline kernel's frame loop, where a per-lane condition becomes a loop-carried lane mask
+    // (alpha_wave_normalise).  Each lane reports what its own columns hold.
+    auto is_nan = [](float x) { return (int)(((__float_as_uint(x) & 0x7fffffffu) + 0x007fffffu) >> 31); };
+#pragma unroll
+    for (int i = 0; i < NV; ++i) bad |= is_nan(r[i]);                // (columns >= V hold -inf, not NaN)
+    for (int v = 64 * NV + lane; v < V; v += 64) bad |= is_nan(row[v]);
   }
   if (ROWS) {                                   // every symbol's value: only the gradient kernel reads these
 #pragma unroll
@@ -461,7 +487,7 @@ __global__ __launch_bounds__(256) void ctc_normalise_wide_kernel(const float* __
   const int b = ctc_normalise_wide_frame<ROWS>(logits + (size_t)f * V, ROWS ? lpn_ws + ((size_t)n * T + t) * V : nullptr,
                                                lps_ws + ((size_t)n * T + t) * S_max, targets + tgt_offsets[n], S, V, blank,
                                                log_probs_in, lane);
-  if (b && lane == 0) atomicOr(&bad[n], 1);
+  if (b) atomicOr(&bad[n], 1);     // (poisoned frames only; any lane that saw it reports)
 }
 
 // mode: bit 0 = the reversed recursion (beta), bit 1 = the workspace already holds this call's normalised log-probabilities
@@ -674,17 +700,26 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_grad_kernel(const float* __re
   const int32_t* tg = targets + tgt_offsets[n];
   const float go = grad_nll[n];
 
+  int bad = 0;   // as in ctc_alpha_kernel: a non-finite normaliser, or a NaN among given log-probabilities; through buf1[0]
+  if (tid == 0) buf1[0] = 0.f;
+  __syncthreads();
   for (int t = tid; t < Tn; t += CTC_THREADS) {
+    const float* row = logits + ((size_t)t * N + n) * V;
     // CTCLoss(dim != -1): the values are what torch.nn.CTCLoss takes as log-probabilities; its backward still returns
     // exp(lp) - exp(log sum alpha beta + nll - lp) (aten/native/LossCTC.cpp), which is what is written here -- the
     // log-softmax over the other axis is chained behind it by ms_log_softmax_axis_backward
-    if (log_probs_in) { logz[t] = 0.f; continue; }
-    const float* row = logits + ((size_t)t * N + n) * V;
+    if (log_probs_in) {
+      for (int v = 0; v < V; ++v) bad |= (row[v] != row[v]) ? 1 : 0;
+      logz[t] = 0.f;
+      continue;
+    }
     float m = neg_inf();
     for (int v = 0; v < V; ++v) m = fmaxf(m, row[v]);
     float sum = 0.f;
     for (int v = 0; v < V; ++v) sum += expf(row[v] - m);
-    logz[t] = logf(sum) + m;
+    const float lz = logf(sum) + m;
+    bad |= (fabsf(lz) < INFINITY) ? 0 : 1;
+    logz[t] = lz;
   }
   for (int s = tid; s < S; s += CTC_THREADS) {
     ext[s] = (s & 1) ? tg[s >> 1] : blank;
@@ -695,8 +730,19 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_grad_kernel(const float* __re
     const size_t t = i / V, v = i - t * V;
     grad[(t * N + n) * V + v] = 0.f;
   }
+  if (bad) buf1[0] = 1.f;
   __syncthreads();
+  const bool poisoned = buf1[0] != 0.f;   // (buf1 is next written behind the barrier that follows frame 0's alphas)
   if (Tn == 0) return;
+  if (poisoned) {
+    // a NaN loss: NaN in every gradient element of the existing frames, as ctc_grad_rows_kernel writes and torch gives (once
+    // alpha + beta is NaN everywhere the bucket maximum below stays -inf and the rows would come out as softmax . go: finite)
+    for (size_t i = tid; i < (size_t)Tn * V; i += CTC_THREADS) {
+      const size_t t = i / V, v = i - t * V;
+      grad[(t * N + n) * V + v] = __uint_as_float(0x7fc00000u);
+    }
+    return;
+  }
   {
     const float* row = logits + (size_t)n * V;
     if (tid == 0) buf0[0] = row[blank] - logz[0];
