@@ -1021,7 +1021,7 @@ int ms_rnnt_align_joint(const float* enc_p, const float* pred_p, const float* w_
  * outputs are ms_lstm_backward_steps' bits.
  *
  * Errors: NULL pointers (other than the optional ones above) and non-positive shapes MS_ERR_INVALID, a short workspace
- * MS_ERR_WORKSPACE.  Out of scope: GRU / tanh cells, a single-launch recurrence, mixed precision. */
+ * MS_ERR_WORKSPACE.  Out of scope: a single-launch recurrence, mixed precision (GRU / tanh cells: the next block). */
 size_t ms_lstm_recompute_workspace_bytes(int T, int N, int H);
 int ms_lstm_recompute(const float* x, const float* h, const float* h0, const float* c0, const int32_t* lens,
                       const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* gates, float* c,
@@ -1037,6 +1037,67 @@ int ms_lstm_backward_steps_bidir(const float* gates, const float* c, const float
                                  const int32_t* lens, int max_len, float* dG, float* d_h0, float* d_c0, float* d_b, int T,
                                  int N, int H, void* stream);
 int ms_embedding_backward(const float* d_out, const int32_t* idx, float* d_table, int R, int D, int V1, void* stream);
+
+/* ---- GRU backward through time (csrc/gru_backward.hip): what lets a loss reach the shipped DeepSpeech2's recurrent stack.
+ *      OWN specification; restated in float64 numpy by tests/gru_backward_ref.py.
+ *
+ * One layer of torch.nn.GRU, float32 throughout, weights in torch layout and read as stored (no packed copy):
+ * w_ih [3H, In], w_hh [3H, H], b_ih / b_hh [3H] or NULL (zeros), gate order r, z, n:
+ *   r = sigmoid(x w_ir^T + b_ir + h_prev w_hr^T + b_hr)
+ *   z = sigmoid(x w_iz^T + b_iz + h_prev w_hz^T + b_hz)
+ *   q = h_prev w_hn^T + b_hn
+ *   n = tanh(x w_in^T + b_in + r q)
+ *   h_t = (1 - z) n + z h_prev
+ * Any H, In, N, T >= 1.  lens [N] int32 on the device, sorted descending, or NULL (every sequence has T steps), with the
+ * LSTM entries' meaning: rows t >= lens[n] of the output are 0 and carry no gradient, h_n is the state at lens[n] - 1 for
+ * direction 0 and at t = 0 for the reverse direction.  The reverse direction is the same cell walked from lens[n] - 1 down
+ * to 0: h_prev(t) = h[t + 1], and h0[1][n] at t = lens[n] - 1.
+ *
+ * Backward, direction 0, for t = lens[n] - 1 down to 0 (the reverse direction mirrors it from t = 0 up to lens[n] - 1):
+ *   dh_t  = d_out[t] + z_{t+1} dh_{t+1} + dGh_{t+1} w_hh     (at t == lens[n] - 1: d_out[t] + d_hn, nothing carried in)
+ *   da_n  = dh_t (1 - z)(1 - n^2)
+ *   da_z  = dh_t (h_prev - n) z (1 - z)
+ *   da_r  = da_n q r (1 - r)
+ *   dGi_t = [da_r, da_z, da_n]        (the gradient of the input-side pre-activations)
+ *   dGh_t = [da_r, da_z, da_n r]      (the gradient of the hidden-side ones)
+ *   d_h0  = z_0 dh_0 + dGh_0 w_hh
+ * d_b_ih / d_b_hh are the column sums of dGi / dGh.  The batch products that finish the layer -- dx = dGi w_ih,
+ * d_w_ih = dGi^T x, d_w_hh = dGh^T h_prev -- are ordinary GEMMs over T N rows and are left to ms_linear_forward.
+ *
+ * ms_gru_recompute.  The forward saves no gates; this call rebuilds one direction's from x [T,N,In] and that direction's
+ * contiguous output h [T,N,H] (h0 [N,H], NULL = zeros).  Every h_prev is known, so the pre-activations of all steps are two
+ * batch products over T N rows (the exact float32 MFMA GEMM behind ms_linear_forward) into the workspace
+ * (ms_gru_recompute_workspace_bytes: two [T N, 3H] planes, each rounded up to 256 bytes; 0 for non-positive shapes).  With
+ * reverse = 1 the recurrent plane is the product of h[t + 1] into rows 0 .. T - 2 and of h0 into row T - 1, the one row that
+ * product leaves free; without h0 the step a direction starts on takes the bias alone.  Then ONE elementwise kernel over
+ * (t, n, j) with t < lens[n], exact expf / tanhf, writes gates [T,N,3H] (activated r, z, n) and q [T,N,H]: nothing is carried,
+ * so unlike the LSTM recompute there is no scan.  Rows past a length are not written, and nothing in them is read by
+ * ms_gru_backward_steps.
+ *
+ * ms_gru_backward_steps.  ndir is 1 or 2.  gates [ndir,T,N,3H]; q and h [ndir,T,N,H], direction major (for ndir == 1 h is the
+ * layer's output itself); h0 and d_hn [ndir,N,H] or NULL; w_hh_rev NULL when ndir == 1; d_out [T,N,ndir H] as autograd hands
+ * the layer's output gradient over -- direction d is read at column d H + j, no slicing pass.  Outputs, always fully written:
+ * dGi and dGh [ndir,T,N,3H], rows t >= lens[n] exact zeros; d_h0 [ndir,N,H] (it also carries z dh between the launches);
+ * d_b_ih and d_b_hh [ndir,3H].  max_len = lens[0] (T without lens) is the number of steps the backward runs.
+ * Launches: max_len + 1 on a (ceil(H / 32), ndir) grid; launch s serves t = max_len - 1 - s of direction 0 and t = s of
+ * direction 1, the last one the d_h0 products (direction 1 reads each sequence's OWN row lens[n] - 1 of dGh).  Stream order is
+ * the only dependency between them -- no grid barrier, no spin wait, no persistent kernel.  A workgroup owns 32 hidden units
+ * for every n at every step, so the bias sums and the carried z dh are plain read-modify-writes: no atomics, the same inputs
+ * give the same bits, and direction 0's outputs of an ndir == 2 call are the ndir == 1 call's bits on the same direction-0
+ * inputs.  The product is float32 MFMA over K = 3H (never split planes); rows of dGh are read in 16-byte quads where H % 4 == 0
+ * and dGh is 16-byte aligned, element by element otherwise -- the same bits either way.  Neither call synchronises or allocates.
+ *
+ * Errors: NULL pointers (other than the optional ones above), non-positive shapes, reverse outside {0, 1}, ndir outside
+ * {1, 2}, max_len outside [1, T] (or != T without lens) MS_ERR_INVALID; a short workspace MS_ERR_WORKSPACE.  Out of scope: a
+ * single-launch recurrence, a K-split of the step product across workgroups, mixed precision. */
+size_t ms_gru_recompute_workspace_bytes(int T, int N, int H);
+int ms_gru_recompute(const float* x, const float* h, const float* h0, const int32_t* lens, const float* w_ih,
+                     const float* w_hh, const float* b_ih, const float* b_hh, float* gates, float* q, int T, int N, int In,
+                     int H, int reverse, void* workspace, size_t workspace_bytes, void* stream);
+int ms_gru_backward_steps(const float* gates, const float* q, const float* h, const float* h0, const float* w_hh_fwd,
+                          const float* w_hh_rev, const float* d_out, const float* d_hn, const int32_t* lens, int max_len,
+                          float* dGi, float* dGh, float* d_h0, float* d_b_ih, float* d_b_hh, int T, int N, int H, int ndir,
+                          void* stream);
 
 /* ---- training: convolution and lookahead backward (csrc/conv_backward.hip) -- OWN specification ---------------------
  *

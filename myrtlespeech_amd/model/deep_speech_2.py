@@ -103,7 +103,8 @@ class DeepSpeech2(torch.nn.Module):
         """``differentiable=True``: the same chain as autograd nodes on the device (``model/conv_autograd.py``,
         ``model/rnn_autograd.py``), so ``CTCLoss()((out, lens), (y, y_lens)).backward()`` fills the gradient of every parameter
         and of ``hx``; the input features are data and get none.  ValueError, before a device is needed, for what has no
-        backward here: GRU / tanh / ``HardLSTM`` stacks, dropout in training mode, ``groups > 1``, and a ``cnn`` or
+        backward here: ``HardLSTM`` stacks, GRU / tanh stacks unless ``self.rnn.gru_backward = True`` (the opt-in switch of
+        ``RNN``: fine-tuning the shipped GRU configuration is that one line), dropout in training mode, ``groups > 1``, and a ``cnn`` or
         ``lookahead`` holding modules other than the builder's own.  The default path is untouched."""
         if differentiable:
             return self._forward_train(x, hx)
@@ -114,7 +115,8 @@ class DeepSpeech2(torch.nn.Module):
         from myrtlespeech_amd.model.rnn import RNN, RNNType
         what = "DeepSpeech2.forward(differentiable=True)"
         rnn, fc = self.rnn, self.fully_connected
-        if not isinstance(rnn, RNN) or rnn.rnn_type != RNNType.LSTM:
+        # (GRU and tanh stacks pass with the stack's opt-in switch on: RNN.forward then sends them to gru_train)
+        if not isinstance(rnn, RNN) or (rnn.rnn_type != RNNType.LSTM and not rnn.gru_backward):
             raise ValueError(f"{what} serves LSTM stacks only (GRU and tanh cells and HardLSTM have no backward in this project)")
         if rnn.batch_first:
             raise ValueError(f"{what} takes a time-major recurrent stack (batch_first=False), as the builder makes it")

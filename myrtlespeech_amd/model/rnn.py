@@ -356,6 +356,9 @@ class RNN(torch.nn.Module):
         self._workspace = _lib.Workspace()
         self.check_status = True
         self.inplace_state = False      # streaming graphs: write h_n / c_n over the hx tensors they were given (run_layers)
+        # opt-in: forward(differentiable=True) sends GRU and tanh stacks to rnn_autograd.gru_train.  Off by default because the
+        # refusal of those cells is pinned by earlier tests; a later test-maintenance change may flip it.  No builder sets it.
+        self.gru_backward = False
         self.use_cuda = torch.cuda.is_available()
         if self.use_cuda:
             self.rnn = self.rnn.cuda()
@@ -378,14 +381,16 @@ class RNN(torch.nn.Module):
         sequence's length are 0, ``hid`` holds each sequence's last valid state.
 
         ``differentiable=True``: the same values as an autograd node (``rnn_autograd.rnn_train``; LSTM stacks only, refused
-        with ValueError otherwise), so a loss reaches the input, ``hx`` and every parameter.  ``batch_first`` is two torch
-        transposes, which autograd sees.  The default path is untouched."""
+        with ValueError otherwise), so a loss reaches the input, ``hx`` and every parameter.  With ``self.gru_backward = True``
+        GRU and tanh stacks go to ``rnn_autograd.gru_train`` instead of being refused (``hid`` is then one tensor, as on the
+        default path).  ``batch_first`` is two torch transposes, which autograd sees.  The default path is untouched."""
         if differentiable:
-            from myrtlespeech_amd.model.rnn_autograd import rnn_train      # (that module imports this one)
+            from myrtlespeech_amd.model.rnn_autograd import gru_train, rnn_train      # (that module imports this one)
             inp, lengths = x
             if inp.dim() != 3:
                 raise ValueError(f"the input must have three dimensions, got {tuple(inp.shape)}")
-            out, hid = rnn_train(self, inp.transpose(0, 1) if self.batch_first else inp, lengths, hx)
+            train = gru_train if (self.gru_backward and self.rnn_type != RNNType.LSTM) else rnn_train
+            out, hid = train(self, inp.transpose(0, 1) if self.batch_first else inp, lengths, hx)
             return (out.transpose(0, 1) if self.batch_first else out, lengths), hid
         _lib.require_gpu()
         inp, lengths = x

@@ -24,9 +24,16 @@ its ``Hardtanh`` fused, whose backward passes dy where the saved OUTPUT is stric
 convolutions and the lookahead have their nodes in ``model/conv_autograd.py`` (``maskconv_train``, ``lookahead_train``), and
 ``DeepSpeech2.forward(..., differentiable=True)`` strings all of them together.
 
-Out of scope, and refused with ValueError before a device is needed: GRU and tanh cells, ``HardLSTM``, inter-layer dropout
-in training mode (``lstm_train`` also refuses ``bidirectional=True``: ``rnn_train`` serves it), convolutions with
-``groups > 1``.  There is no dropout mask, no single-launch (persistent) backward recurrence and no mixed-precision gradient.
+``gru_train(rnn, x, lens, hx)`` is the same for GRU and tanh stacks of either kind (``_GRUStackFunction``: per layer
+``ms_gru_recompute`` per direction, ONE ``ms_gru_backward_steps`` and the batch products; OWN specification: the comment on
+``ms_gru_recompute`` in the header, restated by tests/gru_backward_ref.py).  It is opt-in: ``rnn_train`` and ``lstm_train``
+keep refusing those cells because earlier tests pin the refusals, and ``RNN.forward(differentiable=True)`` /
+``DeepSpeech2.forward(differentiable=True)`` reach it only with ``rnn.gru_backward = True``.
+
+Out of scope, and refused with ValueError before a device is needed: ``HardLSTM``, inter-layer dropout in training mode
+(``lstm_train`` also refuses ``bidirectional=True``: ``rnn_train`` serves it; both refuse GRU and tanh cells: ``gru_train``
+serves them), convolutions with ``groups > 1``.  There is no dropout mask, no single-launch (persistent) backward recurrence
+and no mixed-precision gradient.
 """
 from typing import Optional, Tuple
 
@@ -180,27 +187,32 @@ def embedding_train(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return _EmbeddingFunction.apply(table, idx)
 
 
-def _stack_forward(ctx, ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat):
-    """The forward of both stack nodes: ``run_layers`` one layer at a time, every layer's output kept for the backward."""
+def _stack_forward(ctx, ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat, cell=_lib.CELL_LSTM):
+    """The forward of every stack node: ``run_layers`` one layer at a time, every layer's output kept for the backward.
+    ``cell`` is the stack's own (``CELL_GRU`` / ``CELL_RNN_TANH``: there is no ``c``, ``c0`` is None and ``(out, h_n)`` comes
+    back), so the values are the default path's."""
+    lstm = cell == _lib.CELL_LSTM
     nl = rnn.rnn.num_layers
     hidden = rnn.rnn.hidden_size
     params = rnn._layer_params()
     xin = _lib.f32c(x.detach())
     h0d = _lib.f32c(h0.detach()) if has_hx else None
-    c0d = _lib.f32c(c0.detach()) if has_hx else None
+    c0d = _lib.f32c(c0.detach()) if (has_hx and lstm) else None
     layer_in, hns, cns = [xin], [], []
     for layer in range(nl):
         sl = slice(ndir * layer, ndir * (layer + 1))
-        out, hn, cn = run_layers(_lib.CELL_LSTM, layer_in[-1], lens_dev, max_len, [params[layer]], [rnn._packed[layer]], hidden,
+        out, hn, cn = run_layers(cell, layer_in[-1], lens_dev, max_len, [params[layer]], [rnn._packed[layer]], hidden,
                                  None if h0d is None else h0d[sl], None if c0d is None else c0d[sl],
                                  rnn._workspace, rnn.check_status, ragged=ragged)
         layer_in.append(out.contiguous())
         hns.append(hn)
         cns.append(cn)
     weights = [None if p is None else _lib.f32c(p.detach()) for p in flat]
-    ctx.save_for_backward(*layer_in, *([h0d, c0d] if has_hx else []), *[w for w in weights if w is not None])
-    ctx.meta = dict(nl=nl, hidden=hidden, lens_dev=lens_dev, max_len=max_len, has_hx=has_hx,
+    ctx.save_for_backward(*layer_in, *(([h0d, c0d] if lstm else [h0d]) if has_hx else []), *[w for w in weights if w is not None])
+    ctx.meta = dict(nl=nl, hidden=hidden, lens_dev=lens_dev, max_len=max_len, has_hx=has_hx, lstm=lstm,
                     has_w=[w is not None for w in weights], like=(x, h0, c0) + tuple(flat))
+    if not lstm:
+        return layer_in[-1], torch.cat(hns, 0)
     return layer_in[-1], torch.cat(hns, 0), torch.cat(cns, 0)
 
 
@@ -212,8 +224,8 @@ def _stack_saved(ctx):
     pos = m["nl"] + 1
     h0 = c0 = None
     if m["has_hx"]:
-        h0, c0 = saved[pos], saved[pos + 1]
-        pos += 2
+        h0, c0 = saved[pos], (saved[pos + 1] if m["lstm"] else None)
+        pos += 2 if m["lstm"] else 1
     weights = []
     for has in m["has_w"]:
         weights.append(saved[pos] if has else None)
@@ -377,8 +389,103 @@ class _BiLSTMStackFunction(torch.autograd.Function):
         return _stack_grads(ctx, d_top, torch.cat(d_h0s, 0), torch.cat(d_c0s, 0), w_grads)
 
 
-def _checked_lens(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx) -> torch.Tensor:
-    """The host lengths of a time-major batch for ``rnn``, after every shape check that needs no device."""
+class _GRUStackFunction(torch.autograd.Function):
+    """GRU and tanh stacks of either kind.  Per layer, top down: ``ms_gru_recompute`` per direction (gates and q from the
+    layer's own output), ONE ``ms_gru_backward_steps`` (both recurrences in the same launches, the ``[T, N, ndir H]`` output
+    gradient read in place) and the batch products per direction through ``gemm_nt``.  ``flat`` holds four tensors per layer
+    and direction: (w_ih, w_hh, b_ih, b_hh), direction 0 first.  A tanh layer runs on ``tanh_rnn_as_gru``'s parameters: with
+    exact ``expf`` its r is exactly 1 and its z exactly 0, so da_r, da_z and the carried z dh are exact zeros, the layer's
+    gradients are the n-block rows ``[2H:3H]`` of the GRU's, and dx / d_h0 are used as they are."""
+
+    @staticmethod
+    def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, x, h0, *flat):
+        ctx.tanh = rnn.rnn_type == RNNType.BASIC_RNN
+        ctx.ndir = 2 if rnn.bidirectional else 1
+        # (the GRU form of a tanh layer is the cached one the forward itself runs on where that width has a persistent kernel)
+        ctx.as_gru = [pk.tanh_as_gru(lp) for pk, lp in zip(rnn._packed, rnn._layer_params())] if ctx.tanh else None
+        return _stack_forward(ctx, ctx.ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, None, flat,
+                              cell=_lib.CELL_RNN_TANH if ctx.tanh else _lib.CELL_GRU)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out, d_hn):
+        m = ctx.meta
+        nl, hidden, lens_dev, max_len, ndir = m["nl"], m["hidden"], m["lens_dev"], m["max_len"], ctx.ndir
+        layer_in, h0, _, weights = _stack_saved(ctx)
+        lib = _lib.load()
+        t, n, _ = layer_in[0].shape
+        rows, h3 = t * n, 3 * hidden
+        ws = torch.empty(lib.ms_gru_recompute_workspace_bytes(t, n, hidden), dtype=torch.uint8, device="cuda")      # transient
+        gates = torch.empty((ndir, t, n, h3), dtype=torch.float32, device="cuda")
+        q = torch.empty((ndir, t, n, hidden), dtype=torch.float32, device="cuda")
+        steps = torch.arange(t, device="cuda")[:, None]
+        live = (steps < lens_dev[None, :]).unsqueeze(-1)            # [T, N, 1]: the rows that exist
+        final = (steps == lens_dev[None, :] - 1).unsqueeze(-1)      # ... and each sequence's last one
+        zero = torch.zeros((), dtype=torch.float32, device="cuda")
+        pad = torch.zeros((1, n, hidden), dtype=torch.float32, device="cuda")
+        d_top = _lib.f32c(d_out)
+        d_hn = None if d_hn is None else _lib.f32c(d_hn)
+        d_h0s = [None] * nl
+        w_grads = [None] * (4 * ndir * nl)
+        for layer in range(nl - 1, -1, -1):
+            own = [tuple(weights[4 * (ndir * layer + d):4 * (ndir * layer + d) + 4]) for d in range(ndir)]
+            lw = ctx.as_gru[layer] if ctx.tanh else own      # per direction (w_ih, w_hh, b_ih, b_hh) of the GRU
+            xl, out = layer_in[layer], layer_in[layer + 1]
+            in_size = xl.shape[2]
+            sl = slice(ndir * layer, ndir * (layer + 1))
+            h0l = None if h0 is None else h0[sl].contiguous()
+            # each direction's [T, N, H] output, direction major (a unidirectional layer's is the output itself)
+            hs = out[None] if ndir == 1 else torch.stack([out[..., :hidden], out[..., hidden:]], 0)
+            for d in range(ndir):
+                w_ih, w_hh, b_ih, b_hh = lw[d]
+                _lib.check(lib.ms_gru_recompute(_lib.ptr(xl), _lib.ptr(hs[d]), _lib.ptr(None if h0l is None else h0l[d]),
+                                                _lib.ptr(lens_dev), _lib.ptr(w_ih), _lib.ptr(w_hh), _lib.ptr(b_ih), _lib.ptr(b_hh),
+                                                _lib.ptr(gates[d]), _lib.ptr(q[d]), t, n, in_size, hidden, d, _lib.ptr(ws),
+                                                ws.numel(), _lib.stream_ptr()), "ms_gru_recompute")
+            d_gi = torch.empty((ndir, t, n, h3), dtype=torch.float32, device="cuda")
+            d_gh = torch.empty((ndir, t, n, h3), dtype=torch.float32, device="cuda")
+            d_h0 = torch.empty((ndir, n, hidden), dtype=torch.float32, device="cuda")
+            d_bi = torch.empty((ndir, h3), dtype=torch.float32, device="cuda")
+            d_bh = torch.empty((ndir, h3), dtype=torch.float32, device="cuda")
+            _lib.check(lib.ms_gru_backward_steps(_lib.ptr(gates), _lib.ptr(q), _lib.ptr(hs), _lib.ptr(h0l), _lib.ptr(lw[0][1]),
+                                                 _lib.ptr(lw[1][1] if ndir == 2 else None), _lib.ptr(d_top),
+                                                 _lib.ptr(None if d_hn is None else d_hn[sl].contiguous()), _lib.ptr(lens_dev),
+                                                 max_len, _lib.ptr(d_gi), _lib.ptr(d_gh), _lib.ptr(d_h0), _lib.ptr(d_bi),
+                                                 _lib.ptr(d_bh), t, n, hidden, ndir, _lib.stream_ptr()), "ms_gru_backward_steps")
+            # (dGi is exactly 0 in the rows past a length and the layers' outputs are 0 there; what the CALLER left in those
+            # rows of x may be anything, a NaN included, and must not reach the sum)
+            x_rows = (torch.where(live, xl, zero) if layer == 0 else xl).reshape(rows, in_size).t()
+            # h_prev: direction 0 is h shifted down with h0[0] in row 0; the reverse direction is h shifted UP, and its
+            # initial state sits at each sequence's last live row
+            h_prev = [torch.cat([pad if h0l is None else h0l[0][None], hs[0][:-1]], 0)]
+            if ndir == 2:
+                h_prev.append(torch.where(final, zero if h0l is None else h0l[1][None], torch.cat([hs[1][1:], pad], 0)))
+            need_dx = layer > 0 or ctx.needs_input_grad[5]
+            own_rows = slice(2 * hidden, h3) if ctx.tanh else slice(None)
+            dx = None
+            for d in range(ndir):
+                gi2 = d_gi[d].reshape(rows, h3)
+                base = 4 * (ndir * layer + d)
+                w_grads[base] = gemm_nt(gi2.t().contiguous(), x_rows)[own_rows]
+                w_grads[base + 1] = gemm_nt(d_gh[d].reshape(rows, h3).t().contiguous(), h_prev[d].reshape(rows, hidden).t())[own_rows]
+                w_grads[base + 2] = d_bi[d][own_rows] if own[d][2] is not None else None
+                w_grads[base + 3] = d_bh[d][own_rows] if own[d][3] is not None else None
+                if need_dx:
+                    part = gemm_nt(gi2, lw[d][0].t())
+                    dx = part if dx is None else dx + part
+            d_h0s[layer] = d_h0
+            if need_dx:
+                d_top = dx.reshape(t, n, in_size)
+        x_like, h_like = m["like"][:2]
+        grads = [None if (g is None or like is None or not ctx.needs_input_grad[7 + k]) else _like(g, like)
+                 for k, (g, like) in enumerate(zip(w_grads, m["like"][3:]))]
+        return (None, None, None, None, None, _like(d_top, x_like) if ctx.needs_input_grad[5] else None,
+                _like(torch.cat(d_h0s, 0), h_like) if (m["has_hx"] and ctx.needs_input_grad[6]) else None, *grads)
+
+
+def _checked_lens(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx, single_state: bool = False) -> torch.Tensor:
+    """The host lengths of a time-major batch for ``rnn``, after every shape check that needs no device (``single_state``: the
+    cell has no ``c``, so ``hx`` is ONE tensor)."""
     if x.dim() != 3 or x.shape[2] != rnn.rnn.input_size or min(x.shape) <= 0:
         raise ValueError(f"x must be [T, N, In] with In = {rnn.rnn.input_size}, got {tuple(x.shape)}")
     t, n, _ = x.shape
@@ -392,7 +499,10 @@ def _checked_lens(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx) -> torch.Te
     if int(lens_cpu.min()) < 1 or int(lens_cpu.max()) > t:
         raise ValueError(f"lengths must be in [1, {t}]")
     states, hidden = rnn.rnn.num_layers * (2 if rnn.bidirectional else 1), rnn.rnn.hidden_size
-    if hx is not None:
+    if hx is not None and single_state:
+        if not isinstance(hx, torch.Tensor) or tuple(hx.shape) != (states, n, hidden):
+            raise ValueError(f"hx must be ONE tensor [{states}, {n}, {hidden}] (a GRU or tanh stack has no cell state)")
+    elif hx is not None:
         if len(hx) != 2 or any(tuple(s.shape) != (states, n, hidden) for s in hx):
             raise ValueError(f"hx must be (h0, c0), each [{states}, {n}, {hidden}]")
     return lens_cpu
@@ -443,3 +553,26 @@ def lstm_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple
     if rnn.batch_first:
         raise ValueError("lstm_train takes time-major input (batch_first=False)")
     return _stack_train(rnn, x, lens, hx)
+
+
+def gru_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[torch.Tensor] = None
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``rnn_train`` for GRU and tanh (``RNNType.BASIC_RNN``) stacks of either kind: x [T, N, In] TIME-MAJOR (whatever
+    ``rnn.batch_first`` says), lens [N] sorted descending, hx ONE tensor [num_layers * ndir, N, H] or None (zeros) ->
+    ``(out [T, N, ndir H], h_n)`` with ``RNN.forward``'s values, differentiable in x, hx and every parameter, the ``_reverse``
+    ones included (``_GRUStackFunction``: ``ms_gru_recompute`` / ``ms_gru_backward_steps``).  ``rnn_train`` and ``lstm_train``
+    keep refusing these cells -- earlier tests pin that -- so this entry is explicit, and ``RNN.forward(differentiable=True)``
+    reaches it only with ``rnn.gru_backward = True``.  ValueError, before a device is needed: LSTM stacks (``rnn_train``
+    serves them), ``HardLSTM``, inter-layer dropout in training mode, bad shapes or lengths."""
+    if not isinstance(rnn, RNN):
+        raise ValueError(f"gru_train serves RNN modules, not {type(rnn).__name__} (HardLSTM has no backward in this project)")
+    if rnn.rnn_type == RNNType.LSTM:
+        raise ValueError("gru_train serves GRU and tanh stacks; an LSTM stack goes through rnn_train")
+    if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
+        raise ValueError("gru_train does not serve inter-layer dropout in training mode")
+    lens_cpu = _checked_lens(rnn, x, lens, hx, single_state=True)
+    _lib.require_gpu()
+    max_len = int(lens_cpu[0])
+    flat = [p for layer in rnn._layer_params() for d in layer for p in d]
+    return _GRUStackFunction.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None, x, hx,
+                                   *flat)
