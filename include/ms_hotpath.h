@@ -1038,7 +1038,7 @@ int ms_lstm_backward_steps_bidir(const float* gates, const float* c, const float
                                  int N, int H, void* stream);
 int ms_embedding_backward(const float* d_out, const int32_t* idx, float* d_table, int R, int D, int V1, void* stream);
 
-/* ---- GRU backward through time (csrc/gru_backward.hip): what lets a loss reach the shipped DeepSpeech2's recurrent stack.
+/* ---- GRU backward through time (csrc/rnn_backward.hip): what lets a loss reach the shipped DeepSpeech2's recurrent stack.
  *      OWN specification; restated in float64 numpy by tests/gru_backward_ref.py.
  *
  * One layer of torch.nn.GRU, float32 throughout, weights in torch layout and read as stored (no packed copy):

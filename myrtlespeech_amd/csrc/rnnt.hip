@@ -3,6 +3,7 @@
 // (myrtlespeech_amd/model/rnnt.py, Graves 2012) and parity is against oracle/rnnt_oracle.py only.
 //
 //   ms_embedding_forward   : out[r,:] = table[idx[r],:]                       (gather)
+//   ms_embedding_backward  : d_table[v,:] = sum of d_out[r,:] over idx[r] == v     (one workgroup per row v, r in order)
 //   ms_rnnt_joint_forward  : logp[r,:] = log_softmax(W_o . tanh(enc_p[enc_row[r]] + pred_p[r]) + b_o)
 //                            one workgroup per hypothesis row, tanh vector staged in LDS,
 //                            each wave owns output symbols v = wave, wave+4, ... (lanes split J)
@@ -20,6 +21,20 @@ __global__ void embedding_kernel(const float* __restrict__ table, const int32_t*
   int i = idx[r];
   i = min(max(i, 0), V1 - 1);
   for (int k = threadIdx.x; k < D; k += blockDim.x) out[(size_t)r * D + k] = table[(size_t)i * D + k];
+}
+
+// d_table[v, :] = sum over r with clamp(idx[r]) == v of d_out[r, :], in the order of r.  grid = V1.
+__global__ __launch_bounds__(128) void embedding_backward_kernel(const float* __restrict__ d_out, const int32_t* __restrict__ idx,
+                                                                 float* __restrict__ d_table, int R, int D, int V1) {
+  const int v = blockIdx.x;
+  for (int k = threadIdx.x; k < D; k += blockDim.x) {
+    float s = 0.f;
+    for (int r = 0; r < R; ++r) {
+      const int i = min(max(idx[r], 0), V1 - 1);      // embedding_kernel's rule
+      if (i == v) s += d_out[(size_t)r * D + k];
+    }
+    d_table[(size_t)v * D + k] = s;
+  }
 }
 
 __device__ __forceinline__ float wave_sum_f(float v) {
@@ -109,6 +124,15 @@ extern "C" int ms_embedding_forward(const float* table, const int32_t* idx, floa
   MS_REQUIRE(table && idx && out, "null pointer");
   MS_REQUIRE(R > 0 && D > 0 && V1 > 0, "bad shape");
   hipLaunchKernelGGL(embedding_kernel, dim3(R), dim3(128), 0, (hipStream_t)stream, table, idx, out, D, V1);
+  MS_LAUNCH_CHECK();
+  return MS_OK;
+}
+
+extern "C" int ms_embedding_backward(const float* d_out, const int32_t* idx, float* d_table, int R, int D, int V1,
+                                     void* stream) {
+  MS_REQUIRE(d_out && idx && d_table, "null pointer");
+  MS_REQUIRE(R > 0 && D > 0 && V1 > 0, "bad shape");
+  hipLaunchKernelGGL(embedding_backward_kernel, dim3(V1), dim3(128), 0, (hipStream_t)stream, d_out, idx, d_table, R, D, V1);
   MS_LAUNCH_CHECK();
   return MS_OK;
 }

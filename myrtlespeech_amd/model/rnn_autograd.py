@@ -59,6 +59,20 @@ def _like(g: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
     return g.to(device=ref.device, dtype=ref.dtype).reshape(ref.shape)
 
 
+def _linear_grads(ctx, dy, x, w):
+    """(dx, dw, db) of y = x w^T + b from dy, for the inputs ``ctx.like`` = (x, w, b) that want one."""
+    x_like, w_like, b_like = ctx.like
+    need = ctx.needs_input_grad
+    dx = _like(gemm_nt(dy, w.t()), x_like) if need[0] else None
+    dy_t = dy.t().contiguous() if (need[1] or (b_like is not None and need[2])) else None
+    dw = _like(gemm_nt(dy_t, x.t()), w_like) if need[1] else None
+    db = None
+    if b_like is not None and need[2]:
+        ones = torch.ones((1, dy.shape[0]), dtype=torch.float32, device="cuda")
+        db = _like(gemm_nt(ones, dy_t), b_like)
+    return dx, dw, db
+
+
 class _LinearFunction(torch.autograd.Function):
     """y = x w^T + b; backward: dx = dy w, dw = dy^T x, db = 1^T dy, each a product of ``ms_linear_forward``."""
 
@@ -75,17 +89,7 @@ class _LinearFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        x_like, w_like, b_like = ctx.like
-        dy = _lib.f32c(dy)
-        need = ctx.needs_input_grad
-        dx = _like(gemm_nt(dy, w.t()), x_like) if need[0] else None
-        dy_t = dy.t().contiguous() if (need[1] or (b_like is not None and need[2])) else None
-        dw = _like(gemm_nt(dy_t, x.t()), w_like) if need[1] else None
-        db = None
-        if b_like is not None and need[2]:
-            ones = torch.ones((1, dy.shape[0]), dtype=torch.float32, device="cuda")
-            db = _like(gemm_nt(ones, dy_t), b_like)
-        return dx, dw, db
+        return _linear_grads(ctx, _lib.f32c(dy), x, w)
 
 
 def linear_train(x2d: torch.Tensor, lin: torch.nn.Linear) -> torch.Tensor:
@@ -144,18 +148,9 @@ class _LinearClampFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
-        x_like, w_like, b_like = ctx.like
         lo, hi = ctx.clamp
         dy = torch.where((y > lo) & (y < hi), _lib.f32c(dy), torch.zeros((), dtype=torch.float32, device="cuda"))
-        need = ctx.needs_input_grad
-        dx = _like(gemm_nt(dy, w.t()), x_like) if need[0] else None
-        dy_t = dy.t().contiguous() if (need[1] or (b_like is not None and need[2])) else None
-        dw = _like(gemm_nt(dy_t, x.t()), w_like) if need[1] else None
-        db = None
-        if b_like is not None and need[2]:
-            ones = torch.ones((1, dy.shape[0]), dtype=torch.float32, device="cuda")
-            db = _like(gemm_nt(ones, dy_t), b_like)
-        return dx, dw, db, None, None
+        return (*_linear_grads(ctx, dy, x, w), None, None)
 
 
 def linear_clamp_train(x2d: torch.Tensor, lin: torch.nn.Linear, lo: float, hi: float) -> torch.Tensor:
@@ -234,158 +229,131 @@ def _stack_saved(ctx):
 
 
 def _stack_grads(ctx, d_top, d_h0, d_c0, w_grads):
-    """The backward's return value: gradients shaped and typed like the inputs they belong to, None where none is wanted."""
+    """The backward's return value: gradients shaped and typed like the inputs they belong to, None where none is wanted.  A
+    node's inputs are (rnn, lens_dev, max_len, ragged, has_hx, x, h0[, c0], *flat): a GRU or tanh node has no ``c0`` slot."""
     m = ctx.meta
     x_like, h_like, c_like = m["like"][:3]
-    dx = _like(d_top, x_like) if ctx.needs_input_grad[5] else None
-    dh0 = _like(d_h0, h_like) if (m["has_hx"] and ctx.needs_input_grad[6]) else None
-    dc0 = _like(d_c0, c_like) if (m["has_hx"] and ctx.needs_input_grad[7]) else None
+    need = ctx.needs_input_grad
+    dx = _like(d_top, x_like) if need[5] else None
+    states = [_like(d_h0, h_like) if (m["has_hx"] and need[6]) else None]
+    if m["lstm"]:
+        states.append(_like(d_c0, c_like) if (m["has_hx"] and need[7]) else None)
+    first = 6 + len(states)
     flat = []
     for k, (g, like) in enumerate(zip(w_grads, m["like"][3:])):
-        flat.append(None if (g is None or like is None or not ctx.needs_input_grad[8 + k]) else _like(g, like))
-    return (None, None, None, None, None, dx, dh0, dc0, *flat)
+        flat.append(None if (g is None or like is None or not need[first + k]) else _like(g, like))
+    return (None, None, None, None, None, dx, *states, *flat)
+
+
+def _empty(*shape):
+    return torch.empty(shape, dtype=torch.float32, device="cuda")
+
+
+def _stack_masks(t, lens_dev, ndir):
+    """(live, final), each [T, N, 1]: the rows that exist, and (bidirectional only) each sequence's last one."""
+    steps = torch.arange(t, device="cuda")[:, None]
+    live = (steps < lens_dev[None, :]).unsqueeze(-1)
+    return live, ((steps == lens_dev[None, :] - 1).unsqueeze(-1) if ndir == 2 else None)
+
+
+def _dir_outputs(out, hidden, ndir):
+    """Each direction's [T, N, H] output, direction major (a unidirectional layer's is the output itself)."""
+    return out[None] if ndir == 1 else torch.stack([out[..., :hidden], out[..., hidden:]], 0)
+
+
+def _layer_products(xl, live, hs, h0l, final, d_gi, d_gh, w_ih, need_dx):
+    """The batch products that finish a layer.  Per direction d: d_w_ih = dGi[d]^T x and d_w_hh = dGh[d]^T h_prev[d] (the
+    LSTM's dGi and dGh are the one dG); and dx = sum over d of dGi[d] w_ih[d], [T, N, In], if ``need_dx`` (None otherwise).
+    ``live`` is given for the stack's first layer only."""
+    ndir, t, n, width = d_gi.shape
+    rows, hidden, in_size = t * n, hs.shape[-1], xl.shape[2]
+    zero = torch.zeros((), dtype=torch.float32, device="cuda")
+    pad = torch.zeros((1, n, hidden), dtype=torch.float32, device="cuda")
+    # (dGi is exactly 0 in the rows past a length and the layers' outputs are 0 there; what the CALLER left in those
+    # rows of x may be anything, a NaN included, and must not reach the sum)
+    x_rows = (xl if live is None else torch.where(live, xl, zero)).reshape(rows, in_size).t()
+    # h_prev: direction 0 is h shifted down with h0[0] in row 0; the reverse direction is h shifted UP, and its
+    # initial state sits at each sequence's last live row
+    h_prev = [torch.cat([pad if h0l is None else h0l[0][None], hs[0][:-1]], 0)]
+    if ndir == 2:
+        h_prev.append(torch.where(final, zero if h0l is None else h0l[1][None], torch.cat([hs[1][1:], pad], 0)))
+    d_w, dx = [], None
+    for d in range(ndir):
+        gi2 = d_gi[d].reshape(rows, width)
+        g_t = gi2.t().contiguous()
+        d_w_ih = gemm_nt(g_t, x_rows)
+        if d_gh is not d_gi:
+            g_t = None      # (the transposed planes are the backward's largest transients: one at a time)
+            g_t = d_gh[d].reshape(rows, width).t().contiguous()
+        d_w.append((d_w_ih, gemm_nt(g_t, h_prev[d].reshape(rows, hidden).t())))
+        g_t = None
+        if need_dx:
+            part = gemm_nt(gi2, w_ih[d].t())
+            dx = part if dx is None else dx + part
+    return d_w, (dx.reshape(t, n, in_size) if need_dx else None)
 
 
 class _LSTMStackFunction(torch.autograd.Function):
+    """LSTM stacks of either kind.  Per layer, top down: the gates and c of each direction from the layer's own output
+    (``ms_lstm_recompute``; bidirectional ``ms_lstm_recompute_dir`` into the halves of gates / c), ONE
+    ``ms_lstm_backward_steps`` (bidirectional ``ms_lstm_backward_steps_bidir``: both recurrences in the same launches, the
+    ``[T, N, 2H]`` output gradient read in place) and the batch products per direction.  ``flat`` holds four tensors per layer
+    and direction: (w_ih, w_hh, b_ih, b_hh), direction 0 first, then the ``_reverse`` ones."""
+
     @staticmethod
     def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, *flat):
-        return _stack_forward(ctx, 1, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat)
+        ctx.ndir = 2 if rnn.bidirectional else 1
+        return _stack_forward(ctx, ctx.ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out, d_hn, d_cn):
-        m = ctx.meta
+        m, ndir = ctx.meta, ctx.ndir
         nl, hidden, lens_dev, max_len = m["nl"], m["hidden"], m["lens_dev"], m["max_len"]
         layer_in, h0, c0, weights = _stack_saved(ctx)
-        lib = _lib.load()
         t, n, _ = layer_in[0].shape
-        rows = t * n
-        nbytes = lib.ms_lstm_recompute_workspace_bytes(t, n, hidden)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")                      # transient
-        gates = torch.empty((t, n, 4 * hidden), dtype=torch.float32, device="cuda")
-        cells = torch.empty((t, n, hidden), dtype=torch.float32, device="cuda")
-        live = (torch.arange(t, device="cuda")[:, None] < lens_dev[None, :]).unsqueeze(-1)     # [T, N, 1]: the rows that exist
+        live, final = _stack_masks(t, lens_dev, ndir)
+        lib, ptr = _lib.load(), _lib.ptr
+        ws = torch.empty(lib.ms_lstm_recompute_workspace_bytes(t, n, hidden), dtype=torch.uint8, device="cuda")      # transient
+        gates, cells = _empty(ndir, t, n, 4 * hidden), _empty(ndir, t, n, hidden)
         d_top = _lib.f32c(d_out)
         d_hn = None if d_hn is None else _lib.f32c(d_hn)
         d_cn = None if d_cn is None else _lib.f32c(d_cn)
         d_h0s, d_c0s = [None] * nl, [None] * nl
-        w_grads = [None] * (4 * nl)
+        w_grads = [None] * (4 * ndir * nl)
         for layer in range(nl - 1, -1, -1):
-            w_ih, w_hh, b_ih, b_hh = weights[4 * layer:4 * layer + 4]
-            xl, hl = layer_in[layer], layer_in[layer + 1]
-            in_size = xl.shape[2]
-            h0l = None if h0 is None else h0[layer].contiguous()
-            c0l = None if c0 is None else c0[layer].contiguous()
-            _lib.check(lib.ms_lstm_recompute(_lib.ptr(xl), _lib.ptr(hl), _lib.ptr(h0l), _lib.ptr(c0l), _lib.ptr(lens_dev),
-                                             _lib.ptr(w_ih), _lib.ptr(w_hh), _lib.ptr(b_ih), _lib.ptr(b_hh), _lib.ptr(gates),
-                                             _lib.ptr(cells), t, n, in_size, hidden, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-                       "ms_lstm_recompute")
-            d_g = torch.empty((t, n, 4 * hidden), dtype=torch.float32, device="cuda")
-            d_h0 = torch.empty((n, hidden), dtype=torch.float32, device="cuda")
-            d_c0 = torch.empty((n, hidden), dtype=torch.float32, device="cuda")
-            d_b = torch.empty(4 * hidden, dtype=torch.float32, device="cuda")
-            _lib.check(lib.ms_lstm_backward_steps(_lib.ptr(gates), _lib.ptr(cells), _lib.ptr(c0l), _lib.ptr(w_hh), _lib.ptr(d_top),
-                                                  _lib.ptr(None if d_hn is None else d_hn[layer].contiguous()),
-                                                  _lib.ptr(None if d_cn is None else d_cn[layer].contiguous()),
-                                                  _lib.ptr(lens_dev), max_len, _lib.ptr(d_g), _lib.ptr(d_h0), _lib.ptr(d_c0),
-                                                  _lib.ptr(d_b), t, n, hidden, _lib.stream_ptr()), "ms_lstm_backward_steps")
-            g2 = d_g.reshape(rows, 4 * hidden)
-            g2_t = g2.t().contiguous()
-            h_prev = torch.cat([(torch.zeros((1, n, hidden), dtype=torch.float32, device="cuda") if h0l is None else h0l[None]),
-                                hl[:-1]], 0)
-            # (dG is exactly 0 in the rows past a length and the layers' outputs are 0 there; what the CALLER left in those
-            # rows of x may be anything, a NaN included, and must not reach the sum)
-            x_rows = torch.where(live, xl, torch.zeros((), dtype=torch.float32, device="cuda")) if layer == 0 else xl
-            w_grads[4 * layer] = gemm_nt(g2_t, x_rows.reshape(rows, in_size).t())
-            w_grads[4 * layer + 1] = gemm_nt(g2_t, h_prev.reshape(rows, hidden).t())
-            w_grads[4 * layer + 2] = d_b if b_ih is not None else None
-            w_grads[4 * layer + 3] = d_b if b_hh is not None else None
-            d_h0s[layer], d_c0s[layer] = d_h0, d_c0
-            if layer > 0 or ctx.needs_input_grad[5]:
-                d_top = gemm_nt(g2, w_ih.t()).reshape(t, n, in_size)
-        return _stack_grads(ctx, d_top, torch.stack(d_h0s, 0), torch.stack(d_c0s, 0), w_grads)
-
-
-class _BiLSTMStackFunction(torch.autograd.Function):
-    """``_LSTMStackFunction`` for bidirectional stacks: per layer two ``ms_lstm_recompute_dir`` calls into the halves of
-    gates / c, ONE ``ms_lstm_backward_steps_bidir`` (both recurrences in the same launches) and the batch products per
-    direction.  ``flat`` holds eight tensors per layer: direction 0's (w_ih, w_hh, b_ih, b_hh), then the ``_reverse`` ones."""
-
-    @staticmethod
-    def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, *flat):
-        return _stack_forward(ctx, 2, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d_out, d_hn, d_cn):
-        m = ctx.meta
-        nl, hidden, lens_dev, max_len = m["nl"], m["hidden"], m["lens_dev"], m["max_len"]
-        layer_in, h0, c0, weights = _stack_saved(ctx)
-        lib = _lib.load()
-        t, n, _ = layer_in[0].shape
-        rows = t * n
-        nbytes = lib.ms_lstm_recompute_workspace_bytes(t, n, hidden)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")                      # transient
-        gates = torch.empty((2, t, n, 4 * hidden), dtype=torch.float32, device="cuda")
-        cells = torch.empty((2, t, n, hidden), dtype=torch.float32, device="cuda")
-        steps = torch.arange(t, device="cuda")[:, None]
-        live = (steps < lens_dev[None, :]).unsqueeze(-1)            # [T, N, 1]: the rows that exist
-        final = (steps == lens_dev[None, :] - 1).unsqueeze(-1)      # ... and each sequence's last one
-        zero = torch.zeros((), dtype=torch.float32, device="cuda")
-        d_top = _lib.f32c(d_out)
-        d_hn = None if d_hn is None else _lib.f32c(d_hn)
-        d_cn = None if d_cn is None else _lib.f32c(d_cn)
-        d_h0s, d_c0s = [None] * nl, [None] * nl
-        w_grads = [None] * (8 * nl)
-        for layer in range(nl - 1, -1, -1):
-            lw = weights[8 * layer:8 * layer + 8]
-            xl, out = layer_in[layer], layer_in[layer + 1]
-            in_size = xl.shape[2]
-            sl = slice(2 * layer, 2 * layer + 2)
+            lw = [weights[4 * (ndir * layer + d):4 * (ndir * layer + d) + 4] for d in range(ndir)]      # per direction
+            xl, hs = layer_in[layer], _dir_outputs(layer_in[layer + 1], hidden, ndir)
+            sl = slice(ndir * layer, ndir * (layer + 1))      # this layer's states of the stack's [num_layers * ndir, N, H]
             h0l = None if h0 is None else h0[sl].contiguous()
             c0l = None if c0 is None else c0[sl].contiguous()
-            hs = [out[..., :hidden].contiguous(), out[..., hidden:].contiguous()]      # each direction's [T, N, H] output
-            for d in (0, 1):
-                w_ih, w_hh, b_ih, b_hh = lw[4 * d:4 * d + 4]
-                _lib.check(lib.ms_lstm_recompute_dir(_lib.ptr(xl), _lib.ptr(hs[d]), _lib.ptr(None if h0l is None else h0l[d]),
-                                                     _lib.ptr(None if c0l is None else c0l[d]), _lib.ptr(lens_dev), _lib.ptr(w_ih),
-                                                     _lib.ptr(w_hh), _lib.ptr(b_ih), _lib.ptr(b_hh), _lib.ptr(gates[d]),
-                                                     _lib.ptr(cells[d]), t, n, in_size, hidden, d, _lib.ptr(ws), ws.numel(),
-                                                     _lib.stream_ptr()), "ms_lstm_recompute_dir")
-            d_g = torch.empty((2, t, n, 4 * hidden), dtype=torch.float32, device="cuda")
-            d_h0 = torch.empty((2, n, hidden), dtype=torch.float32, device="cuda")
-            d_c0 = torch.empty((2, n, hidden), dtype=torch.float32, device="cuda")
-            d_b = torch.empty((2, 4 * hidden), dtype=torch.float32, device="cuda")
-            _lib.check(lib.ms_lstm_backward_steps_bidir(_lib.ptr(gates), _lib.ptr(cells), _lib.ptr(c0l), _lib.ptr(lw[1]), _lib.ptr(lw[5]),
-                                                        _lib.ptr(d_top), _lib.ptr(None if d_hn is None else d_hn[sl].contiguous()),
-                                                        _lib.ptr(None if d_cn is None else d_cn[sl].contiguous()),
-                                                        _lib.ptr(lens_dev), max_len, _lib.ptr(d_g), _lib.ptr(d_h0), _lib.ptr(d_c0),
-                                                        _lib.ptr(d_b), t, n, hidden, _lib.stream_ptr()),
-                       "ms_lstm_backward_steps_bidir")
-            # (dG is exactly 0 in the rows past a length and the layers' outputs are 0 there; what the CALLER left in those
-            # rows of x may be anything, a NaN included, and must not reach the sum)
-            x_rows = (torch.where(live, xl, zero) if layer == 0 else xl).reshape(rows, in_size).t()
-            pad = torch.zeros((1, n, hidden), dtype=torch.float32, device="cuda")
-            # h_prev: direction 0 is h shifted down with h0[0] in row 0; the reverse direction is h shifted UP, and its
-            # initial state sits at each sequence's last live row
-            h_prev = [torch.cat([pad if h0l is None else h0l[0][None], hs[0][:-1]], 0),
-                      torch.where(final, zero if h0l is None else h0l[1][None], torch.cat([hs[1][1:], pad], 0))]
-            need_dx = layer > 0 or ctx.needs_input_grad[5]
-            dx = None
-            for d in (0, 1):
-                g2 = d_g[d].reshape(rows, 4 * hidden)
-                g2_t = g2.t().contiguous()
-                base = 8 * layer + 4 * d
-                w_grads[base] = gemm_nt(g2_t, x_rows)
-                w_grads[base + 1] = gemm_nt(g2_t, h_prev[d].reshape(rows, hidden).t())
-                w_grads[base + 2] = d_b[d] if lw[4 * d + 2] is not None else None
-                w_grads[base + 3] = d_b[d] if lw[4 * d + 3] is not None else None
-                if need_dx:
-                    part = gemm_nt(g2, lw[4 * d].t())
-                    dx = part if dx is None else dx + part
+            for d in range(ndir):
+                w_ih, w_hh, b_ih, b_hh = lw[d]
+                args = (ptr(xl), ptr(hs[d]), ptr(None if h0l is None else h0l[d]), ptr(None if c0l is None else c0l[d]),
+                        ptr(lens_dev), ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(gates[d]), ptr(cells[d]), t, n, xl.shape[2],
+                        hidden)
+                if ndir == 1:
+                    _lib.check(lib.ms_lstm_recompute(*args, ptr(ws), ws.numel(), _lib.stream_ptr()), "ms_lstm_recompute")
+                else:
+                    _lib.check(lib.ms_lstm_recompute_dir(*args, d, ptr(ws), ws.numel(), _lib.stream_ptr()), "ms_lstm_recompute_dir")
+            d_g, d_b = _empty(ndir, t, n, 4 * hidden), _empty(ndir, 4 * hidden)
+            d_h0, d_c0 = _empty(ndir, n, hidden), _empty(ndir, n, hidden)
+            steps, name = ((lib.ms_lstm_backward_steps, "ms_lstm_backward_steps") if ndir == 1 else
+                           (lib.ms_lstm_backward_steps_bidir, "ms_lstm_backward_steps_bidir"))
+            _lib.check(steps(ptr(gates), ptr(cells), ptr(c0l), *(ptr(w[1]) for w in lw), ptr(d_top),
+                             ptr(None if d_hn is None else d_hn[sl].contiguous()),
+                             ptr(None if d_cn is None else d_cn[sl].contiguous()), ptr(lens_dev), max_len, ptr(d_g),
+                             ptr(d_h0), ptr(d_c0), ptr(d_b), t, n, hidden, _lib.stream_ptr()), name)
+            d_w, dx = _layer_products(xl, live if layer == 0 else None, hs, h0l, final, d_g, d_g, [w[0] for w in lw],
+                                        layer > 0 or ctx.needs_input_grad[5])
+            for d in range(ndir):
+                base = 4 * (ndir * layer + d)
+                w_grads[base], w_grads[base + 1] = d_w[d]
+                w_grads[base + 2] = d_b[d] if lw[d][2] is not None else None
+                w_grads[base + 3] = d_b[d] if lw[d][3] is not None else None
             d_h0s[layer], d_c0s[layer] = d_h0, d_c0
-            if need_dx:
-                d_top = dx.reshape(t, n, in_size)
+            if dx is not None:
+                d_top = dx
         return _stack_grads(ctx, d_top, torch.cat(d_h0s, 0), torch.cat(d_c0s, 0), w_grads)
 
 
@@ -409,78 +377,49 @@ class _GRUStackFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out, d_hn):
-        m = ctx.meta
-        nl, hidden, lens_dev, max_len, ndir = m["nl"], m["hidden"], m["lens_dev"], m["max_len"], ctx.ndir
-        layer_in, h0, _, weights = _stack_saved(ctx)
-        lib = _lib.load()
+        m, ndir = ctx.meta, ctx.ndir
+        nl, hidden, lens_dev, max_len = m["nl"], m["hidden"], m["lens_dev"], m["max_len"]
+        layer_in, h0, c0, weights = _stack_saved(ctx)
         t, n, _ = layer_in[0].shape
-        rows, h3 = t * n, 3 * hidden
+        live, final = _stack_masks(t, lens_dev, ndir)
+        lib, ptr = _lib.load(), _lib.ptr
+        h3 = 3 * hidden
         ws = torch.empty(lib.ms_gru_recompute_workspace_bytes(t, n, hidden), dtype=torch.uint8, device="cuda")      # transient
-        gates = torch.empty((ndir, t, n, h3), dtype=torch.float32, device="cuda")
-        q = torch.empty((ndir, t, n, hidden), dtype=torch.float32, device="cuda")
-        steps = torch.arange(t, device="cuda")[:, None]
-        live = (steps < lens_dev[None, :]).unsqueeze(-1)            # [T, N, 1]: the rows that exist
-        final = (steps == lens_dev[None, :] - 1).unsqueeze(-1)      # ... and each sequence's last one
-        zero = torch.zeros((), dtype=torch.float32, device="cuda")
-        pad = torch.zeros((1, n, hidden), dtype=torch.float32, device="cuda")
+        gates, q = _empty(ndir, t, n, h3), _empty(ndir, t, n, hidden)
         d_top = _lib.f32c(d_out)
         d_hn = None if d_hn is None else _lib.f32c(d_hn)
         d_h0s = [None] * nl
         w_grads = [None] * (4 * ndir * nl)
+        own_rows = slice(2 * hidden, h3) if ctx.tanh else slice(None)
         for layer in range(nl - 1, -1, -1):
             own = [tuple(weights[4 * (ndir * layer + d):4 * (ndir * layer + d) + 4]) for d in range(ndir)]
             lw = ctx.as_gru[layer] if ctx.tanh else own      # per direction (w_ih, w_hh, b_ih, b_hh) of the GRU
-            xl, out = layer_in[layer], layer_in[layer + 1]
-            in_size = xl.shape[2]
-            sl = slice(ndir * layer, ndir * (layer + 1))
+            xl, hs = layer_in[layer], _dir_outputs(layer_in[layer + 1], hidden, ndir)
+            sl = slice(ndir * layer, ndir * (layer + 1))      # this layer's states of the stack's [num_layers * ndir, N, H]
             h0l = None if h0 is None else h0[sl].contiguous()
-            # each direction's [T, N, H] output, direction major (a unidirectional layer's is the output itself)
-            hs = out[None] if ndir == 1 else torch.stack([out[..., :hidden], out[..., hidden:]], 0)
             for d in range(ndir):
                 w_ih, w_hh, b_ih, b_hh = lw[d]
-                _lib.check(lib.ms_gru_recompute(_lib.ptr(xl), _lib.ptr(hs[d]), _lib.ptr(None if h0l is None else h0l[d]),
-                                                _lib.ptr(lens_dev), _lib.ptr(w_ih), _lib.ptr(w_hh), _lib.ptr(b_ih), _lib.ptr(b_hh),
-                                                _lib.ptr(gates[d]), _lib.ptr(q[d]), t, n, in_size, hidden, d, _lib.ptr(ws),
-                                                ws.numel(), _lib.stream_ptr()), "ms_gru_recompute")
-            d_gi = torch.empty((ndir, t, n, h3), dtype=torch.float32, device="cuda")
-            d_gh = torch.empty((ndir, t, n, h3), dtype=torch.float32, device="cuda")
-            d_h0 = torch.empty((ndir, n, hidden), dtype=torch.float32, device="cuda")
-            d_bi = torch.empty((ndir, h3), dtype=torch.float32, device="cuda")
-            d_bh = torch.empty((ndir, h3), dtype=torch.float32, device="cuda")
-            _lib.check(lib.ms_gru_backward_steps(_lib.ptr(gates), _lib.ptr(q), _lib.ptr(hs), _lib.ptr(h0l), _lib.ptr(lw[0][1]),
-                                                 _lib.ptr(lw[1][1] if ndir == 2 else None), _lib.ptr(d_top),
-                                                 _lib.ptr(None if d_hn is None else d_hn[sl].contiguous()), _lib.ptr(lens_dev),
-                                                 max_len, _lib.ptr(d_gi), _lib.ptr(d_gh), _lib.ptr(d_h0), _lib.ptr(d_bi),
-                                                 _lib.ptr(d_bh), t, n, hidden, ndir, _lib.stream_ptr()), "ms_gru_backward_steps")
-            # (dGi is exactly 0 in the rows past a length and the layers' outputs are 0 there; what the CALLER left in those
-            # rows of x may be anything, a NaN included, and must not reach the sum)
-            x_rows = (torch.where(live, xl, zero) if layer == 0 else xl).reshape(rows, in_size).t()
-            # h_prev: direction 0 is h shifted down with h0[0] in row 0; the reverse direction is h shifted UP, and its
-            # initial state sits at each sequence's last live row
-            h_prev = [torch.cat([pad if h0l is None else h0l[0][None], hs[0][:-1]], 0)]
-            if ndir == 2:
-                h_prev.append(torch.where(final, zero if h0l is None else h0l[1][None], torch.cat([hs[1][1:], pad], 0)))
-            need_dx = layer > 0 or ctx.needs_input_grad[5]
-            own_rows = slice(2 * hidden, h3) if ctx.tanh else slice(None)
-            dx = None
+                _lib.check(lib.ms_gru_recompute(ptr(xl), ptr(hs[d]), ptr(None if h0l is None else h0l[d]), ptr(lens_dev), ptr(w_ih),
+                                                ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(gates[d]), ptr(q[d]), t, n, xl.shape[2], hidden,
+                                                d, ptr(ws), ws.numel(), _lib.stream_ptr()), "ms_gru_recompute")
+            d_gi, d_gh = _empty(ndir, t, n, h3), _empty(ndir, t, n, h3)
+            d_h0, d_bi, d_bh = _empty(ndir, n, hidden), _empty(ndir, h3), _empty(ndir, h3)
+            _lib.check(lib.ms_gru_backward_steps(ptr(gates), ptr(q), ptr(hs), ptr(h0l), ptr(lw[0][1]),
+                                                 ptr(lw[1][1] if ndir == 2 else None), ptr(d_top),
+                                                 ptr(None if d_hn is None else d_hn[sl].contiguous()), ptr(lens_dev), max_len,
+                                                 ptr(d_gi), ptr(d_gh), ptr(d_h0), ptr(d_bi), ptr(d_bh), t, n, hidden, ndir,
+                                                 _lib.stream_ptr()), "ms_gru_backward_steps")
+            d_w, dx = _layer_products(xl, live if layer == 0 else None, hs, h0l, final, d_gi, d_gh, [w[0] for w in lw],
+                                        layer > 0 or ctx.needs_input_grad[5])
             for d in range(ndir):
-                gi2 = d_gi[d].reshape(rows, h3)
                 base = 4 * (ndir * layer + d)
-                w_grads[base] = gemm_nt(gi2.t().contiguous(), x_rows)[own_rows]
-                w_grads[base + 1] = gemm_nt(d_gh[d].reshape(rows, h3).t().contiguous(), h_prev[d].reshape(rows, hidden).t())[own_rows]
+                w_grads[base], w_grads[base + 1] = d_w[d][0][own_rows], d_w[d][1][own_rows]
                 w_grads[base + 2] = d_bi[d][own_rows] if own[d][2] is not None else None
                 w_grads[base + 3] = d_bh[d][own_rows] if own[d][3] is not None else None
-                if need_dx:
-                    part = gemm_nt(gi2, lw[d][0].t())
-                    dx = part if dx is None else dx + part
             d_h0s[layer] = d_h0
-            if need_dx:
-                d_top = dx.reshape(t, n, in_size)
-        x_like, h_like = m["like"][:2]
-        grads = [None if (g is None or like is None or not ctx.needs_input_grad[7 + k]) else _like(g, like)
-                 for k, (g, like) in enumerate(zip(w_grads, m["like"][3:]))]
-        return (None, None, None, None, None, _like(d_top, x_like) if ctx.needs_input_grad[5] else None,
-                _like(torch.cat(d_h0s, 0), h_like) if (m["has_hx"] and ctx.needs_input_grad[6]) else None, *grads)
+            if dx is not None:
+                d_top = dx
+        return _stack_grads(ctx, d_top, torch.cat(d_h0s, 0), None, w_grads)
 
 
 def _checked_lens(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx, single_state: bool = False) -> torch.Tensor:
@@ -509,17 +448,14 @@ def _checked_lens(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx, single_stat
 
 
 def _stack_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx):
-    """The autograd node of an LSTM stack the caller has vetted: ``_LSTMStackFunction`` or ``_BiLSTMStackFunction``."""
+    """The autograd node of an LSTM stack the caller has vetted (``_LSTMStackFunction``)."""
     lens_cpu = _checked_lens(rnn, x, lens, hx)
     _lib.require_gpu()
     max_len = int(lens_cpu[0])
-    if rnn.bidirectional:
-        node, flat = _BiLSTMStackFunction, [p for layer in rnn._layer_params() for d in layer for p in d]
-    else:
-        node, flat = _LSTMStackFunction, [p for layer in rnn._layer_params() for p in layer[0]]
+    flat = [p for layer in rnn._layer_params() for d in layer for p in d]
     h0, c0 = hx if hx is not None else (None, None)
-    out, hn, cn = node.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None, x, h0, c0,
-                             *flat)
+    out, hn, cn = _LSTMStackFunction.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None,
+                                           x, h0, c0, *flat)
     return out, (hn, cn)
 
 

@@ -306,7 +306,7 @@ def layer_backward(p, x, h0, c0, lens, d_out, d_hn, d_cn):
 
 
 # name: T, N, H, In, bias, state (h0 / c0 given), d_hn, d_cn, lens kind.  The step kernel's tiles are 32 hidden units x 32
-# batch rows; H in {8, 40, 72} and N in {1, 3, 33} lie on both sides of each, every option appears in both settings.
+# batch rows; H in {7, 8, 40, 72} and N in {1, 3, 33} lie on both sides of each, every option appears in both settings.
 _CASES = (
     ("t1_n1_h8", 1, 1, 8, 5, True, False, False, False, None),
     ("t2_n3_h40_equal", 2, 3, 40, 33, False, True, True, True, "equal"),
@@ -317,6 +317,8 @@ _CASES = (
     ("t1_n3_h72_equal", 1, 3, 72, 5, True, True, True, True, "equal"),
     ("t9_n1_h40_short", 9, 1, 40, 5, True, True, True, True, "short"),
     ("t9_n33_h40_ragged", 9, 33, 40, 33, True, False, True, True, "ragged"),
+    # odd H: the product's last k-octet is half empty (4H / 8 = 3.5), over two passes of batch rows
+    ("t9_n33_h7_ragged", 9, 33, 7, 5, True, True, True, True, "ragged"),
 )
 CASE_NAMES = tuple(c[0] for c in _CASES)
 
