@@ -1143,6 +1143,69 @@ int ms_lookahead_backward(const float* x, const float* w, const float* y, const 
                           int T, int ctx, long xs_n, long xs_f, long xs_t, long ys_n, long ys_f, long ys_t, int act,
                           float act_lo, float act_hi, void* stream);
 
+/* ---- training: gradient norm, clip and the fused optimizer steps (csrc/optim.hip) -- OWN specification -----------------
+ *
+ * A tensor LIST is a host array of n device pointers (one array per role: parameters, gradients, each state) plus the host
+ * array numels_host of n element counts.  Every tensor is float32, contiguous and 4-byte aligned -- NOT necessarily 16-byte
+ * aligned: parameters may be views at odd offsets; the kernels move 16-byte quads where an array's body is so aligned and
+ * single elements elsewhere, with the same bits either way.  A count may be 0 (the tensor is skipped; its pointers are not
+ * read) and must be below 2^40.  The lists travel to the kernels by value, 48 tensors per launch; there is no device table.
+ * Nothing synchronises, allocates or reads back.  Every multiply and add below is ONE rounded float32 operation (the file is
+ * built with -ffp-contract=off), square root and division are correctly rounded (plain sqrtf and /, not __fsqrt_rn): tests/optim_ref.py restates the arithmetic
+ * in numpy and the device is held to it bit for bit.
+ *
+ * ms_grad_norm: norm_out[0] = sqrtf(S), S the float32 sum of g*g over every element of every tensor; norm_out[1] = 1.0f where
+ *   norm_out[0] is NaN or infinite, else 0.0f.  n == 0 or all-empty lists give {0, 0}.  Order of the additions -- a function of
+ *   numels_host alone, so the same list gives the same bits on every run and at every alignment: a tensor is cut into chunks
+ *   of 4096 elements by element index; in a chunk thread u of 256 adds the quads u, u + 256, .. (a quad is
+ *   ((g0 g0 + g1 g1) + g2 g2) + g3 g3, the 1..3 elements after the last whole quad are summed on their own and added on the
+ *   thread that the next quad would fall to); the 64 lanes of a wave meet in a butterfly (xor 32, 16, .. 1), the four waves
+ *   are added in ascending order: one partial per chunk in the workspace, in list order.  A second launch of one workgroup
+ *   adds the partials the same way (thread u takes partials u, u + 256, ..) and takes the root.
+ *   ms_grad_norm_workspace_bytes is host arithmetic on the counts.
+ *
+ * The clip coefficient of the device word norm[0], in float32:  q = max_norm / (norm[0] + 1e-6f);  c = q where q < 1 or q is
+ *   NaN, else 1.  A NaN norm therefore poisons what it scales (torch.nn.utils.clip_grad_norm_ does the same; fminf(1, q) would
+ *   drop the NaN), an infinite norm gives c = 0.
+ *
+ * ms_grad_clip: g = g * c in place.
+ *
+ * ms_sgd_step, per element (torch.optim.SGD without dampening):
+ *     g' = g * c                      only when norm != NULL; g itself is NOT written
+ *     d  = g' + weight_decay * p      skipped when weight_decay == 0
+ *     b  = momentum * b + d           skipped when momentum == 0 (bufs_host NULL; u = d)
+ *     u  = nesterov ? d + momentum * b : b
+ *     p  = p - lr * u
+ *   Momentum buffers start as zeros (momentum * 0 + d == d: the first step is no special case).
+ *
+ * ms_adam_step, per element (torch.optim.Adam; the caller forms step_size = float32(lr / (1 - beta1^t)) and
+ *   rsqrt_bc2 = float32(sqrt(1 - beta2^t)) in float64, from the FLOAT32 values of the betas -- there is no pow on the device; (1 - beta1) and (1 - beta2) are formed
+ *   in float64 from the float32 arguments, rounded once to float32 on the host and passed to the kernel as scalars):
+ *     g', d as above
+ *     m  = beta1 * m + (1 - beta1) * d
+ *     v  = beta2 * v + ((1 - beta2) * d) * d
+ *     w  = amsgrad ? (vmax = (v > vmax or v is NaN) ? v : vmax) : v       max_exp_avg_sq_host NULL: no amsgrad
+ *     den = sqrt(w) / rsqrt_bc2 + eps
+ *     p  = p - step_size * (m / den)
+ *
+ * Both steps: with skip_nonfinite != 0 and norm[1] != 0 the kernels write NOTHING, neither p nor the state.
+ *
+ * Errors (MS_ERR_INVALID, nothing launched): n < 0, a NULL list that is not optional, a NULL or misaligned pointer of a
+ * non-empty tensor, a count out of range, bufs_host without momentum or momentum without bufs_host, nesterov without momentum,
+ * skip_nonfinite without norm; a short workspace MS_ERR_WORKSPACE.  Out of scope: other dtypes, dampening, decoupled weight
+ * decay, capture of a step into a HIP graph across changing lists, multi-device reduction. */
+size_t ms_grad_norm_workspace_bytes(const int64_t* numels_host, int n);
+int ms_grad_norm(void* const* grads_host, const int64_t* numels_host, int n, float* norm_out, void* workspace,
+                 size_t workspace_bytes, void* stream);
+int ms_grad_clip(void* const* grads_host, const int64_t* numels_host, int n, const float* norm, float max_norm, void* stream);
+int ms_sgd_step(void* const* params_host, void* const* grads_host, void* const* bufs_host, const int64_t* numels_host, int n,
+                float lr, float momentum, float weight_decay, int nesterov, const float* norm, float max_norm,
+                int skip_nonfinite, void* stream);
+int ms_adam_step(void* const* params_host, void* const* grads_host, void* const* exp_avg_host, void* const* exp_avg_sq_host,
+                 void* const* max_exp_avg_sq_host, const int64_t* numels_host, int n, float beta1, float beta2, float eps,
+                 float weight_decay, float step_size, float rsqrt_bc2, const float* norm, float max_norm, int skip_nonfinite,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

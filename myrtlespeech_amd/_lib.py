@@ -154,6 +154,11 @@ SIGNATURES = {
     "ms_standardize_forward": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "ms_context_frames_forward": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "ms_spec_augment_": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
+    "ms_grad_norm_workspace_bytes": (c_size_t, [_P, c_int]),
+    "ms_grad_norm": (c_int, [_P, _P, c_int, _P, _P, c_size_t, _P]),
+    "ms_grad_clip": (c_int, [_P, _P, c_int, _P, c_float, _P]),
+    "ms_sgd_step": (c_int, [_P, _P, _P, _P, c_int, c_float, c_float, c_float, c_int, _P, c_float, c_int, _P]),
+    "ms_adam_step": (c_int, [_P, _P, _P, _P, _P, _P, c_int] + [c_float] * 6 + [_P, c_float, c_int, _P]),
 }
 
 _lib = None

@@ -50,6 +50,7 @@ class SeqToSeq(torch.nn.Module):
         self.loss = loss
         self.pre_process_steps = pre_process_steps
         self.optim = optim
+        self.lr_scheduler = None      # builders/optimizer.py makes one; run/train.py steps it once per training epoch
         self.use_cuda = torch.cuda.is_available()
 
     @property

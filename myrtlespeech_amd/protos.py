@@ -4,7 +4,8 @@ The reference generates ``*_pb2.py`` with ``protoc`` (Dockerfile:28) and never c
 them in; ``protoc`` is not available here.  The schema of the messages the hot path is
 configured with (``protos/{speech_to_text,deep_speech_1,deep_speech_2,rnn,conv_layer,
 fully_connected,lookahead,activation,ctc_loss,ctc_greedy_decoder,ctc_beam_decoder,
-language_model,pre_process_step,stage}.proto``) is restated below as data -- same
+language_model,pre_process_step,stage}.proto``) and of the task around it (``protos/{task_config,train_config,eval_config,
+optimizer,lr_scheduler,dataset,range}.proto``) is restated below as data -- same
 package, message, field and enum names and field numbers, so the reference's
 text-format ``.config`` files parse unchanged -- and turned into message classes through
 ``descriptor_pb2`` + ``message_factory`` in a private descriptor pool (no clash with real
@@ -96,6 +97,44 @@ _SCHEMA = {
                                      {"oneof": "supported_post_processes"}),
                                     ("ctc_beam_decoder", 7, f".{_PKG}.CTCBeamDecoder",
                                      {"oneof": "supported_post_processes"})]},
+        "SGD": {"fields": [("learning_rate", 1, "float", {}), ("momentum", 2, ".google.protobuf.FloatValue", {}),
+                           ("l2_weight_decay", 3, ".google.protobuf.FloatValue", {}), ("nesterov_momentum", 4, "bool", {})]},
+        "Adam": {"fields": [("learning_rate", 1, "float", {}), ("beta_1", 2, ".google.protobuf.FloatValue", {}),
+                            ("beta_2", 3, ".google.protobuf.FloatValue", {}), ("eps", 4, ".google.protobuf.FloatValue", {}),
+                            ("l2_weight_decay", 5, ".google.protobuf.FloatValue", {}), ("amsgrad", 6, "bool", {})]},
+        "ConstantLR": {"fields": []},
+        "StepLR": {"fields": [("step_size", 1, "uint32", {}), ("gamma", 2, ".google.protobuf.FloatValue", {})]},
+        "ExponentialLR": {"fields": [("gamma", 1, "float", {})]},
+        "CosineAnnealingLR": {"fields": [("t_max", 1, "uint32", {}), ("eta_min", 2, ".google.protobuf.FloatValue", {})]},
+        "Range": {"fields": [("lower", 1, "uint32", {}), ("upper", 2, "uint32", {})]},
+        "Dataset": {
+            "nested": {
+                "FakeSpeechToText": {"fields": [("dataset_len", 1, "uint32", {}), ("audio_ms", 2, f".{_PKG}.Range", {}),
+                                                ("label_symbols", 3, "string", {}), ("label_len", 4, f".{_PKG}.Range", {})]},
+                "LibriSpeech": {
+                    "enums": {"SUBSET": ["DEV_CLEAN", "DEV_OTHER", "TEST_CLEAN", "TEST_OTHER", "TRAIN_CLEAN_100",
+                                         "TRAIN_CLEAN_360", "TRAIN_OTHER_500"]},
+                    "fields": [("root", 1, "string", {}),
+                               ("subset", 2, f"enum:.{_PKG}.Dataset.LibriSpeech.SUBSET", {"repeated": True}),
+                               ("max_secs", 3, ".google.protobuf.FloatValue", {})]},
+            },
+            "fields": [("fake_speech_to_text", 1, f".{_PKG}.Dataset.FakeSpeechToText", {"oneof": "supported_datasets"}),
+                       ("librispeech", 2, f".{_PKG}.Dataset.LibriSpeech", {"oneof": "supported_datasets"})],
+        },
+        "TrainConfig": {"fields": [("batch_size", 1, "uint32", {}), ("epochs", 2, "uint32", {}),
+                                   ("sgd", 3, f".{_PKG}.SGD", {"oneof": "supported_optimizers"}),
+                                   ("adam", 4, f".{_PKG}.Adam", {"oneof": "supported_optimizers"}),
+                                   ("constant_lr", 5, f".{_PKG}.ConstantLR", {"oneof": "supported_lr_scheduler"}),
+                                   ("step_lr", 6, f".{_PKG}.StepLR", {"oneof": "supported_lr_scheduler"}),
+                                   ("exponential_lr", 7, f".{_PKG}.ExponentialLR", {"oneof": "supported_lr_scheduler"}),
+                                   ("cosine_annealing_lr", 8, f".{_PKG}.CosineAnnealingLR",
+                                    {"oneof": "supported_lr_scheduler"}),
+                                   ("dataset", 9, f".{_PKG}.Dataset", {}),
+                                   ("shuffle_batches_before_every_epoch", 10, "bool", {"oneof": "supported_shuffles"})]},
+        "EvalConfig": {"fields": [("batch_size", 1, "uint32", {}), ("dataset", 4, f".{_PKG}.Dataset", {})]},
+        "TaskConfig": {"fields": [("speech_to_text", 1, f".{_PKG}.SpeechToText", {"oneof": "supported_models"}),
+                                  ("train_config", 2, f".{_PKG}.TrainConfig", {}),
+                                  ("eval_config", 3, f".{_PKG}.EvalConfig", {})]},
     },
 }
 
@@ -173,6 +212,17 @@ CTCBeamDecoder = _cls("CTCBeamDecoder")
 LanguageModel = _cls("LanguageModel")
 PreProcessStep = _cls("PreProcessStep")
 SpeechToText = _cls("SpeechToText")
+SGD = _cls("SGD")
+Adam = _cls("Adam")
+ConstantLR = _cls("ConstantLR")
+StepLR = _cls("StepLR")
+ExponentialLR = _cls("ExponentialLR")
+CosineAnnealingLR = _cls("CosineAnnealingLR")
+Range = _cls("Range")
+Dataset = _cls("Dataset")
+TrainConfig = _cls("TrainConfig")
+EvalConfig = _cls("EvalConfig")
+TaskConfig = _cls("TaskConfig")
 
 PADDING_MODE_NONE, PADDING_MODE_SAME = 0, 1
 STAGE_TRAIN, STAGE_EVAL, STAGE_TRAIN_AND_EVAL = 0, 1, 2
