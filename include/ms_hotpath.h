@@ -1206,6 +1206,42 @@ int ms_adam_step(void* const* params_host, void* const* grads_host, void* const*
                  float weight_decay, float step_size, float rsqrt_bc2, const float* norm, float max_norm, int skip_nonfinite,
                  void* stream);
 
+/* ---- training: dropout (csrc/dropout.hip) -- OWN specification ------------------------------------------------------------
+ *
+ * Every result is a pure function of its arguments: no generator state on the device, no stored mask, the same bits on every
+ * run and every device, and a backward that RECOMPUTES the mask from the same four numbers.
+ *
+ * Generator: Philox4x32-10 -- multipliers 0xD2511F53 (on word 0) and 0xCD9E8D57 (on word 2), Weyl constants 0x9E3779B9 and
+ *   0xBB67AE85 added to the key words after every round.  Known answers (counter, key -> output, words 0..3):
+ *     0 0 0 0, 0 0                                              -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     ffffffff x 4, ffffffff x 2                                -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     243f6a88 85a308d3 13198a2e 03707344, a4093822 299f31d0    -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * Key and counter: a dropout CALL is (seed: u64, offset: u64).  For the flat element index e of the contiguous array the call
+ *   covers, q = e >> 2 and lane = e & 3; counter = (q_lo, q_hi, offset_lo, offset_hi), key = (seed_lo, seed_hi),
+ *   r = philox(counter, key)[lane].  e is relative to the ARRAY, not to its address: a view at an odd element offset gets the
+ *   same mask.  One offset per call, so calls never overlap whatever their size.
+ * Keep rule: the element is kept iff r >= thr, thr = ceil(p * 2^32) formed on the host in exact integer arithmetic from the
+ *   double p, 0 < p <= 1; thr may be 2^32 (nothing is kept).  The uniform is never converted to float: the mask is exact.
+ * Value: out[e] = x[e] * m[e], m[e] = scale where kept and +0.0f otherwise; scale = float32(1.0 / (1.0 - p)) formed in double
+ *   on the host and rounded once, 0 for p == 1.  ONE float32 multiply, not a select: a NaN or an infinity in a dropped element
+ *   stays visible, as in torch.nn.Dropout.  tests/dropout_ref.py restates all of this in numpy and the device is held to it
+ *   bit for bit.
+ *
+ * ms_dropout_forward: out = x * m over n elements.  out may alias x.  Applied to a gradient with the forward's (thr, scale,
+ *   seed, offset) it IS the backward of dropout: dx = dy * m.
+ * ms_clamp_dropout_backward: dx[e] = (lo < y[e] && y[e] < hi) ? dy[e] * m[e] : 0, y the saved clamped PRE-dropout output of a
+ *   linear layer with a fused clamp: the clamp's gate (a NaN y closes it) and the mask in one pass.
+ *
+ * Every array is float32, contiguous and 4-byte aligned; it moves as 16-byte quads where its base is 16-byte aligned and
+ * element by element otherwise.  One lane owns one Philox quad; the grid is capped at 2048 workgroups of 256 and strides.
+ * Errors (MS_ERR_INVALID, nothing launched): n < 0, a NULL or misaligned pointer with n > 0, thr == 0, thr > 2^32, a negative
+ * or non-finite scale.  n == 0 is MS_OK with no launch.  Out of scope: dropout in a GEMM epilogue, other dtypes, torch's own
+ * mask stream. */
+int ms_dropout_forward(const float* x, float* out, int64_t n, uint64_t thr, float scale, uint64_t seed, uint64_t offset,
+                       void* stream);
+int ms_clamp_dropout_backward(const float* dy, const float* y, float* dx, int64_t n, float lo, float hi, uint64_t thr,
+                              float scale, uint64_t seed, uint64_t offset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ loudly; if there is no HIP device, every op raises ``RuntimeError``.
 import ctypes
 import os
 import re
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_uint64, c_void_p
 
 import torch
 
@@ -159,6 +159,8 @@ SIGNATURES = {
     "ms_grad_clip": (c_int, [_P, _P, c_int, _P, c_float, _P]),
     "ms_sgd_step": (c_int, [_P, _P, _P, _P, c_int, c_float, c_float, c_float, c_int, _P, c_float, c_int, _P]),
     "ms_adam_step": (c_int, [_P, _P, _P, _P, _P, _P, c_int] + [c_float] * 6 + [_P, c_float, c_int, _P]),
+    "ms_dropout_forward": (c_int, [_P, _P, c_int64, c_uint64, c_float, c_uint64, c_uint64, _P]),
+    "ms_clamp_dropout_backward": (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_uint64, c_float, c_uint64, c_uint64, _P]),
 }
 
 _lib = None

@@ -18,6 +18,10 @@ class DeepSpeech1(torch.nn.Module):
     """`Deep Speech 1 <https://arxiv.org/abs/1412.5567>`_ with the paper's
     recurrent layer replaced by an LSTM (deep_speech_1.py:13-188)."""
 
+    # opt-in (model/dropout.py: attach): the source of the dropout masks of forward(differentiable=True) in training mode.
+    # No Module, parameter or buffer: state_dict keys stay as they are.  No builder sets it.
+    dropout_generator = None
+
     def __init__(self, input_features: int, input_channels: int, n_hidden: int, out_features: int, drop_prob: float,
                  relu_clip: float = 20.0, forget_gate_bias: float = 1.0, hard_lstm: bool = False):
         super().__init__()
@@ -51,13 +55,21 @@ class DeepSpeech1(torch.nn.Module):
     def _forward_train(self, x: Tuple[torch.Tensor, torch.Tensor], hx: Optional[RNNState]):
         """``forward`` as a chain of autograd nodes on the device (``model/rnn_autograd.py``): every Linear through the
         exact float32 product with its clamp fused, the bidirectional LSTM through ``rnn_train``.  The input features are
-        data: no gradient is returned for them."""
-        from myrtlespeech_amd.model.rnn_autograd import linear_clamp_train, linear_train
+        data: no gradient is returned for them.  In training mode with ``drop_prob > 0`` and ``self.dropout_generator`` set,
+        fc1 .. fc4 are ``linear_clamp_dropout_train`` (masks over the time-major [T N, units] outputs, offsets in layer
+        order)."""
+        from myrtlespeech_amd.model.rnn_autograd import linear_clamp_dropout_train, linear_clamp_train, linear_train
         if isinstance(self.bi_lstm, HardLSTM):
             raise ValueError("DeepSpeech1.forward(differentiable=True) does not serve hard_lstm=True (HardLSTM has no backward)")
-        if self.training and self._drop_prob > 0:
+        gen = self.dropout_generator if (self.training and self._drop_prob > 0) else None
+        if self.training and self._drop_prob > 0 and gen is None:
             raise ValueError("DeepSpeech1.forward(differentiable=True) does not serve dropout masks: train in .eval() or with "
                              "drop_prob = 0")
+
+        def hidden(h, fc):      # Linear + clipped ReLU (+ Dropout: one offset per layer, in layer order)
+            if gen is None:
+                return linear_clamp_train(h, fc[0], 0.0, self._relu_clip)
+            return linear_clamp_dropout_train(h, fc[0], 0.0, self._relu_clip, self._drop_prob, gen)
         h, seq_lens = x
         if h.dim() != 4 or h.shape[1] * h.shape[2] != self.fc1[0].in_features or min(h.shape) <= 0:
             raise ValueError(f"the input must be [batch, {self.input_channels}, {self.input_features}, seq_len], got {tuple(h.shape)}")
@@ -69,11 +81,11 @@ class DeepSpeech1(torch.nn.Module):
                    "ms_nct_to_tnc")
         h = tnf.reshape(t * n, c * f)
         for fc in (self.fc1, self.fc2, self.fc3):
-            h = linear_clamp_train(h, fc[0], 0.0, self._relu_clip)
+            h = hidden(h, fc)
         # bi_lstm is batch_first: hand it the batch-major view, as the default path does
         (h, _), hid = self.bi_lstm((h.reshape(t, n, -1).transpose(0, 1), seq_lens), hx, differentiable=True)
         h = h.transpose(0, 1).reshape(t * n, -1)
-        h = linear_clamp_train(h, self.fc4[0], 0.0, self._relu_clip)
+        h = hidden(h, self.fc4)
         out = linear_train(h, self.out).reshape(t, n, -1)
         return (out, _lib.lens_to_device(seq_lens)), hid
 
@@ -83,7 +95,8 @@ class DeepSpeech1(torch.nn.Module):
 
         ``differentiable=True``: the same chain and the same structure as autograd nodes on the device, so
         ``CTCLoss()((out, lens), (y, y_lens)).backward()`` fills the gradient of every parameter; ValueError for
-        ``hard_lstm=True`` and for ``drop_prob > 0`` in training mode.  The default path is untouched."""
+        ``hard_lstm=True``, and for ``drop_prob > 0`` in training mode unless a ``DropoutGenerator`` is attached
+        (``model/dropout.py``: ``attach(model, DropoutGenerator(seed))``).  The default path is untouched."""
         if differentiable:
             return self._forward_train(x, hx)
         _lib.require_gpu()

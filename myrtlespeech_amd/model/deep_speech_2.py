@@ -38,6 +38,8 @@ class DeepSpeech2(torch.nn.Module):
     """`Deep Speech 2 <http://proceedings.mlr.press/v48/amodei16.pdf>`_
     (deep_speech_2.py:8-172); argument contract as in the reference."""
 
+    dropout_generator = None      # opt-in (model/dropout.py: attach); no Module, parameter or buffer; no builder sets it
+
     def __init__(self, cnn: Optional[torch.nn.Module], rnn: torch.nn.Module, lookahead: Optional[torch.nn.Module],
                  fully_connected: torch.nn.Module):
         super().__init__()
@@ -104,8 +106,11 @@ class DeepSpeech2(torch.nn.Module):
         ``model/rnn_autograd.py``), so ``CTCLoss()((out, lens), (y, y_lens)).backward()`` fills the gradient of every parameter
         and of ``hx``; the input features are data and get none.  ValueError, before a device is needed, for what has no
         backward here: ``HardLSTM`` stacks, GRU / tanh stacks unless ``self.rnn.gru_backward = True`` (the opt-in switch of
-        ``RNN``: fine-tuning the shipped GRU configuration is that one line), dropout in training mode, ``groups > 1``, and a ``cnn`` or
-        ``lookahead`` holding modules other than the builder's own.  The default path is untouched."""
+        ``RNN``: fine-tuning the shipped GRU configuration is that one line), dropout in training mode with no ``DropoutGenerator``
+        attached (``model/dropout.py``: ``attach(model, generator)`` sets ``self.dropout_generator``, which serves the
+        ``FullyConnected``'s ``Dropout`` modules, and ``self.rnn.dropout_generator``, which serves the inter-layer dropout; the
+        recurrent stack takes its offsets first), ``groups > 1``, and a ``cnn`` or ``lookahead`` holding modules other than the
+        builder's own.  The default path is untouched."""
         if differentiable:
             return self._forward_train(x, hx)
         return self.back(self.front(x), hx)
@@ -120,12 +125,14 @@ class DeepSpeech2(torch.nn.Module):
             raise ValueError(f"{what} serves LSTM stacks only (GRU and tanh cells and HardLSTM have no backward in this project)")
         if rnn.batch_first:
             raise ValueError(f"{what} takes a time-major recurrent stack (batch_first=False), as the builder makes it")
-        if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
+        # (dropout is opt-in: served where a DropoutGenerator is attached -- model/dropout.py -- and refused as ever where not)
+        if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1 and rnn.dropout_generator is None:
             raise ValueError(f"{what} does not serve inter-layer dropout in training mode")
         if not isinstance(fc, FullyConnected):
             raise ValueError(f"{what} serves the builder's FullyConnected, not {type(fc).__name__}")
         fc_mods = [fc.fully_connected] if isinstance(fc.fully_connected, torch.nn.Linear) else list(fc.fully_connected)
-        if fc.training and any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in fc_mods):
+        if (fc.training and any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in fc_mods)
+                and self.dropout_generator is None):
             raise ValueError(f"{what} does not serve dropout masks: train in .eval() or with dropout = 0")
         front = []
         mods = [] if self.cnn is None else (list(self.cnn) if isinstance(self.cnn, torch.nn.Sequential) else [self.cnn])
@@ -175,12 +182,12 @@ class DeepSpeech2(torch.nn.Module):
         seq = seq.reshape(n, c * f, t).permute(2, 0, 1).contiguous()
         (seq, lens), hid = self.rnn((seq, lens), hx, differentiable=True)
         t, n, f = seq.shape
-        fc = self.fully_connected
+        fc, gen = self.fully_connected, self.dropout_generator
         if la is not None:
             ntf = lookahead_train(la[0], seq.contiguous(), la[1])
-            out = linear_stack_train(ntf.reshape(n * t, f), fc.fully_connected, fc.training).reshape(n, t, -1).transpose(0, 1)
+            out = linear_stack_train(ntf.reshape(n * t, f), fc.fully_connected, fc.training, gen).reshape(n, t, -1).transpose(0, 1)
         else:
-            out = linear_stack_train(seq.reshape(t * n, f), fc.fully_connected, fc.training).reshape(t, n, -1)
+            out = linear_stack_train(seq.reshape(t * n, f), fc.fully_connected, fc.training, gen).reshape(t, n, -1)
         return (out, _lib.lens_to_device(lens)), hid
 
     def front(self, x: Tuple[torch.Tensor, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:

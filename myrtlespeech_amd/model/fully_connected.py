@@ -145,6 +145,10 @@ def run_linear_stack(x2d: torch.Tensor, plan, few_rows: bool = False) -> torch.T
 class FullyConnected(torch.nn.Module):
     """A fully connected neural network (fully_connected.py:9-166)."""
 
+    # set by model/dropout.py's attach: what a caller of ``linear_stack_train(x, self.fully_connected, self.training, generator)``
+    # hands over (DeepSpeech2 hands over its own).  ``forward`` is the inference path and never reads it.
+    dropout_generator = None
+
     def __init__(self, in_features: int, out_features: int, num_hidden_layers: int, hidden_size: Optional[int],
                  hidden_activation_fn: Optional[torch.nn.Module], dropout: Optional[float] = None):
         if num_hidden_layers < 0:

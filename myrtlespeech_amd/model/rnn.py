@@ -329,6 +329,10 @@ def _run_layers_halves(lib, cell, x, lens_dev, max_len, layer_params, packed, hi
 class RNN(torch.nn.Module):
     """A recurrent neural network (rnn.py:41-205); see the module docstring."""
 
+    # opt-in (model/dropout.py: attach): the source of the inter-layer dropout masks of forward(differentiable=True) in training
+    # mode; without one that dropout is refused.  No Module, parameter or buffer: state_dict keys stay as they are.
+    dropout_generator = None
+
     def __init__(self, rnn_type: RNNType, input_size: int, hidden_size: int, num_layers: int = 1, bias: bool = True,
                  dropout: float = 0.0, bidirectional: bool = False, forget_gate_bias: Optional[float] = None,
                  batch_first: bool = False):
@@ -383,7 +387,8 @@ class RNN(torch.nn.Module):
         ``differentiable=True``: the same values as an autograd node (``rnn_autograd.rnn_train``; LSTM stacks only, refused
         with ValueError otherwise), so a loss reaches the input, ``hx`` and every parameter.  With ``self.gru_backward = True``
         GRU and tanh stacks go to ``rnn_autograd.gru_train`` instead of being refused (``hid`` is then one tensor, as on the
-        default path).  ``batch_first`` is two torch transposes, which autograd sees.  The default path is untouched."""
+        default path).  ``batch_first`` is two torch transposes, which autograd sees.  Inter-layer dropout in training mode is
+        served from ``self.dropout_generator`` and refused without one.  The default path is untouched."""
         if differentiable:
             from myrtlespeech_amd.model.rnn_autograd import gru_train, rnn_train      # (that module imports this one)
             inp, lengths = x

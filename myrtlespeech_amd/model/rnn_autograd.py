@@ -30,10 +30,19 @@ convolutions and the lookahead have their nodes in ``model/conv_autograd.py`` (`
 keep refusing those cells because earlier tests pin the refusals, and ``RNN.forward(differentiable=True)`` /
 ``DeepSpeech2.forward(differentiable=True)`` reach it only with ``rnn.gru_backward = True``.
 
-Out of scope, and refused with ValueError before a device is needed: ``HardLSTM``, inter-layer dropout in training mode
-(``lstm_train`` also refuses ``bidirectional=True``: ``rnn_train`` serves it; both refuse GRU and tanh cells: ``gru_train``
-serves them), convolutions with ``groups > 1``.  There is no dropout mask, no single-launch (persistent) backward recurrence
-and no mixed-precision gradient.
+Dropout (``model/dropout.py``; OWN specification: the comment on ``ms_dropout_forward`` in the header, restated by
+tests/dropout_ref.py) is opt-in as well: with no ``DropoutGenerator`` attached every entry refuses ``Dropout(p > 0)`` and
+inter-layer dropout in training mode exactly as before.  With one, ``linear_clamp_dropout_train`` is a clamped linear layer with
+its dropout (forward: the product, then ``ms_dropout_forward``; backward: gate and mask in ONE ``ms_clamp_dropout_backward``),
+``linear_stack_train`` serves a chain's ``Dropout`` modules, and the stack nodes drop the output of every layer but the last on
+its way to the next layer.  A stack node saves each layer's UNDROPPED output (its own recurrence reads it as ``h_prev``) and
+the backward remakes the dropped one into a scratch buffer for the next layer's recompute -- one memory-bound pass per layer
+instead of a second saved ``[T, N, ndir H]`` tensor -- and passes the gradient handed down a layer through the same kernel.
+
+Out of scope, and refused with ValueError before a device is needed: ``HardLSTM``, dropout in training mode with no generator
+attached (``lstm_train`` also refuses ``bidirectional=True``: ``rnn_train`` serves it; both refuse GRU and tanh cells:
+``gru_train`` serves them), convolutions with ``groups > 1``.  There is no single-launch (persistent) backward recurrence and no
+mixed-precision gradient.
 """
 from typing import Optional, Tuple
 
@@ -41,6 +50,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from myrtlespeech_amd import _lib
+from myrtlespeech_amd.model.dropout import DropoutGenerator, apply_mask, dropout_call, dropout_train
 from myrtlespeech_amd.model.rnn import RNN, RNNType, run_layers
 
 
@@ -160,16 +170,100 @@ def linear_clamp_train(x2d: torch.Tensor, lin: torch.nn.Linear, lo: float, hi: f
     return _LinearClampFunction.apply(x2d, lin.weight, lin.bias, lo, hi)
 
 
-def linear_stack_train(x2d: torch.Tensor, stack, training: bool = False) -> torch.Tensor:
+class _LinearClampDropoutFunction(torch.autograd.Function):
+    """out = clamp(x w^T + b, lo, hi) * m: ``_LinearClampFunction``'s product into y (saved: the clamped PRE-dropout output),
+    then ``ms_dropout_forward`` into out.  Backward: ``ms_clamp_dropout_backward`` -- dy * m where lo < y < hi strictly, 0
+    elsewhere, the mask remade from ``call`` -- in one pass, then ``_LinearFunction``'s three products."""
+
+    @staticmethod
+    def forward(ctx, x2d, weight, bias, lo, hi, call):
+        x = _lib.f32c(x2d.detach())
+        w = _lib.f32c(weight.detach())
+        b = None if bias is None else _lib.f32c(bias.detach())
+        m, k = x.shape
+        n = w.shape[0]
+        y = torch.empty((m, n), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.load().ms_linear_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), m, k, n, _lib.ACT_CLAMP,
+                                                 float(lo), float(hi), _lib.stream_ptr()), "ms_linear_forward")
+        ctx.save_for_backward(x, w, y)
+        ctx.like = (x2d, weight, bias)
+        ctx.clamp = (float(lo), float(hi))
+        ctx.call = call
+        return apply_mask(y, torch.empty_like(y), call)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        x, w, y = ctx.saved_tensors
+        lo, hi = ctx.clamp
+        thr, scale, seed, offset = ctx.call
+        d_out = _lib.f32c(d_out)
+        dy = torch.empty_like(y)
+        _lib.check(_lib.load().ms_clamp_dropout_backward(_lib.ptr(d_out), _lib.ptr(y), _lib.ptr(dy), y.numel(), lo, hi, thr, scale,
+                                                         seed, offset, _lib.stream_ptr()), "ms_clamp_dropout_backward")
+        return (*_linear_grads(ctx, dy, x, w), None, None, None)
+
+
+def linear_clamp_dropout_train(x2d: torch.Tensor, lin: torch.nn.Linear, lo: float, hi: float, p: float,
+                               generator: DropoutGenerator) -> torch.Tensor:
+    """``Dropout(p)(Hardtanh(lo, hi)(lin(x2d)))`` in training mode for x2d [M, K] as one autograd node on the device; the mask is
+    indexed over the [M, N] output.  Consumes one offset of ``generator``."""
+    if not lo < hi:
+        raise ValueError(f"linear_clamp_dropout_train needs lo < hi, got [{lo}, {hi}]")
+    return _LinearClampDropoutFunction.apply(x2d, lin.weight, lin.bias, lo, hi, dropout_call(p, generator))
+
+
+def _dropout_steps(mods):
+    """[[linear | None, fused clamp | None, dropout p | None], ...] of a Linear / activation / Dropout chain in training mode:
+    a ``Dropout(p > 0)`` joins the layer in front of it, or stands alone (linear None) where there is none to join."""
+    from myrtlespeech_amd.model.utils import activation_clamp
+    steps = []
+    for m in mods:
+        if isinstance(m, torch.nn.Linear):
+            steps.append([m, None, None])
+        elif isinstance(m, torch.nn.Dropout):
+            if m.p > 0:
+                if steps and steps[-1][0] is not None and steps[-1][2] is None:
+                    steps[-1][2] = m.p
+                else:
+                    steps.append([None, None, m.p])
+        else:
+            clamp = activation_clamp(m)
+            if clamp is not None:
+                if not steps or steps[-1][0] is None or steps[-1][1] is not None or steps[-1][2] is not None:
+                    raise NotImplementedError("activation without a preceding Linear")
+                steps[-1][1] = clamp
+    return steps
+
+
+def linear_stack_train(x2d: torch.Tensor, stack, training: bool = False, generator: Optional[DropoutGenerator] = None
+                       ) -> torch.Tensor:
     """``run_linear_stack`` as a chain of autograd nodes: ``stack`` is ``linear_stack_plan``'s list, or the Linear / activation /
     Dropout chain itself (then ``training`` is the owning module's mode).  A layer with a clamp is ``linear_clamp_train``
-    (``ReLU`` is the clamp (0, +inf)), one without ``linear_train``.  ValueError, before a device is needed, for
-    ``Dropout(p > 0)`` in training mode: there is no dropout mask in this project (DeepSpeech1's rule)."""
+    (``ReLU`` is the clamp (0, +inf)), one without ``linear_train``.  ``Dropout(p > 0)`` in training mode: with no ``generator``
+    ValueError, before a device is needed (the rule a user can rely on: no source of randomness attached, no dropout); with
+    one it is applied, fused with the clamp in front of it where there is one (``linear_clamp_dropout_train``) and through
+    ``dropout_train`` otherwise, one offset per application in chain order.  A ``Dropout`` with p == 0, and any in eval mode,
+    launches nothing and consumes no offset."""
     if isinstance(stack, torch.nn.Module):
         from myrtlespeech_amd.model.fully_connected import linear_stack_plan
         mods = [stack] if isinstance(stack, torch.nn.Linear) else list(stack)
         if training and any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in mods):
-            raise ValueError("linear_stack_train does not serve dropout masks: train in .eval() or with dropout = 0")
+            if generator is None:
+                raise ValueError("linear_stack_train does not serve dropout masks: train in .eval() or with dropout = 0")
+            steps = _dropout_steps(mods)
+            _lib.require_gpu()      # (before the first offset is taken: a call that cannot run consumes none)
+            h = x2d
+            for lin, clamp, p in steps:
+                if lin is None:
+                    h = dropout_train(h, p, generator)
+                elif clamp is not None and p is not None:
+                    h = linear_clamp_dropout_train(h, lin, clamp[0], clamp[1], p, generator)
+                else:
+                    h = linear_train(h, lin) if clamp is None else linear_clamp_train(h, lin, clamp[0], clamp[1])
+                    if p is not None:
+                        h = dropout_train(h, p, generator)
+            return h
         stack = linear_stack_plan(stack, training)
     h = x2d
     for lin, clamp in stack:
@@ -182,10 +276,11 @@ def embedding_train(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return _EmbeddingFunction.apply(table, idx)
 
 
-def _stack_forward(ctx, ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat, cell=_lib.CELL_LSTM):
+def _stack_forward(ctx, ndir, rnn, lens_dev, max_len, ragged, has_hx, drop, x, h0, c0, flat, cell=_lib.CELL_LSTM):
     """The forward of every stack node: ``run_layers`` one layer at a time, every layer's output kept for the backward.
     ``cell`` is the stack's own (``CELL_GRU`` / ``CELL_RNN_TANH``: there is no ``c``, ``c0`` is None and ``(out, h_n)`` comes
-    back), so the values are the default path's."""
+    back), so the values are the default path's.  ``drop`` (``_stack_dropout``: one call per layer but the last, or None):
+    layer l + 1 reads layer l's output through ``ms_dropout_forward``; what is KEPT is the undropped output."""
     lstm = cell == _lib.CELL_LSTM
     nl = rnn.rnn.num_layers
     hidden = rnn.rnn.hidden_size
@@ -194,17 +289,21 @@ def _stack_forward(ctx, ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0,
     h0d = _lib.f32c(h0.detach()) if has_hx else None
     c0d = _lib.f32c(c0.detach()) if (has_hx and lstm) else None
     layer_in, hns, cns = [xin], [], []
+    cur = xin
     for layer in range(nl):
         sl = slice(ndir * layer, ndir * (layer + 1))
-        out, hn, cn = run_layers(cell, layer_in[-1], lens_dev, max_len, [params[layer]], [rnn._packed[layer]], hidden,
+        out, hn, cn = run_layers(cell, cur, lens_dev, max_len, [params[layer]], [rnn._packed[layer]], hidden,
                                  None if h0d is None else h0d[sl], None if c0d is None else c0d[sl],
                                  rnn._workspace, rnn.check_status, ragged=ragged)
-        layer_in.append(out.contiguous())
+        cur = out.contiguous()
+        layer_in.append(cur)
+        if drop is not None and layer < nl - 1:
+            cur = apply_mask(cur, torch.empty_like(cur), drop[layer])
         hns.append(hn)
         cns.append(cn)
     weights = [None if p is None else _lib.f32c(p.detach()) for p in flat]
     ctx.save_for_backward(*layer_in, *(([h0d, c0d] if lstm else [h0d]) if has_hx else []), *[w for w in weights if w is not None])
-    ctx.meta = dict(nl=nl, hidden=hidden, lens_dev=lens_dev, max_len=max_len, has_hx=has_hx, lstm=lstm,
+    ctx.meta = dict(nl=nl, hidden=hidden, lens_dev=lens_dev, max_len=max_len, has_hx=has_hx, lstm=lstm, drop=drop,
                     has_w=[w is not None for w in weights], like=(x, h0, c0) + tuple(flat))
     if not lstm:
         return layer_in[-1], torch.cat(hns, 0)
@@ -230,23 +329,46 @@ def _stack_saved(ctx):
 
 def _stack_grads(ctx, d_top, d_h0, d_c0, w_grads):
     """The backward's return value: gradients shaped and typed like the inputs they belong to, None where none is wanted.  A
-    node's inputs are (rnn, lens_dev, max_len, ragged, has_hx, x, h0[, c0], *flat): a GRU or tanh node has no ``c0`` slot."""
+    node's inputs are (rnn, lens_dev, max_len, ragged, has_hx, drop, x, h0[, c0], *flat): a GRU or tanh node has no ``c0`` slot."""
     m = ctx.meta
     x_like, h_like, c_like = m["like"][:3]
     need = ctx.needs_input_grad
-    dx = _like(d_top, x_like) if need[5] else None
-    states = [_like(d_h0, h_like) if (m["has_hx"] and need[6]) else None]
+    dx = _like(d_top, x_like) if need[6] else None
+    states = [_like(d_h0, h_like) if (m["has_hx"] and need[7]) else None]
     if m["lstm"]:
-        states.append(_like(d_c0, c_like) if (m["has_hx"] and need[7]) else None)
-    first = 6 + len(states)
+        states.append(_like(d_c0, c_like) if (m["has_hx"] and need[8]) else None)
+    first = 7 + len(states)
     flat = []
     for k, (g, like) in enumerate(zip(w_grads, m["like"][3:])):
         flat.append(None if (g is None or like is None or not need[first + k]) else _like(g, like))
-    return (None, None, None, None, None, dx, *states, *flat)
+    return (None, None, None, None, None, None, dx, *states, *flat)
 
 
 def _empty(*shape):
     return torch.empty(shape, dtype=torch.float32, device="cuda")
+
+
+def _layer_input(ctx_meta, layer_in, layer, scratch):
+    """What layer ``layer`` read in the forward: the saved tensor, or (a stack with dropout, layer > 0) the layer below's saved
+    output dropped again into ``scratch`` (one [T, N, ndir H] buffer for the whole backward)."""
+    drop = ctx_meta["drop"]
+    if drop is None or layer == 0:
+        return layer_in[layer], scratch
+    if scratch is None:
+        scratch = torch.empty_like(layer_in[layer])
+    return apply_mask(layer_in[layer], scratch, drop[layer - 1]), scratch
+
+
+def _stack_dropout(rnn: RNN, generator: Optional[DropoutGenerator], what: str):
+    """The inter-layer dropout of one forward of ``rnn``: None where there is none to apply (eval mode, ``dropout == 0``, one
+    layer -- no offset is consumed), else one ``dropout_call`` per layer but the last, offsets in ascending layer order, from
+    ``generator`` or ``rnn.dropout_generator``.  ValueError where dropout is due and neither generator is there."""
+    if not (rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1):
+        return None
+    generator = generator if generator is not None else rnn.dropout_generator
+    if generator is None:
+        raise ValueError(f"{what} does not serve inter-layer dropout in training mode")
+    return [dropout_call(rnn.rnn.dropout, generator) for _ in range(rnn.rnn.num_layers - 1)]
 
 
 def _stack_masks(t, lens_dev, ndir):
@@ -301,9 +423,9 @@ class _LSTMStackFunction(torch.autograd.Function):
     and direction: (w_ih, w_hh, b_ih, b_hh), direction 0 first, then the ``_reverse`` ones."""
 
     @staticmethod
-    def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, *flat):
+    def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, drop, x, h0, c0, *flat):
         ctx.ndir = 2 if rnn.bidirectional else 1
-        return _stack_forward(ctx, ctx.ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, c0, flat)
+        return _stack_forward(ctx, ctx.ndir, rnn, lens_dev, max_len, ragged, has_hx, drop, x, h0, c0, flat)
 
     @staticmethod
     @once_differentiable
@@ -321,9 +443,11 @@ class _LSTMStackFunction(torch.autograd.Function):
         d_cn = None if d_cn is None else _lib.f32c(d_cn)
         d_h0s, d_c0s = [None] * nl, [None] * nl
         w_grads = [None] * (4 * ndir * nl)
+        scratch = None
         for layer in range(nl - 1, -1, -1):
             lw = [weights[4 * (ndir * layer + d):4 * (ndir * layer + d) + 4] for d in range(ndir)]      # per direction
-            xl, hs = layer_in[layer], _dir_outputs(layer_in[layer + 1], hidden, ndir)
+            xl, scratch = _layer_input(m, layer_in, layer, scratch)
+            hs = _dir_outputs(layer_in[layer + 1], hidden, ndir)
             sl = slice(ndir * layer, ndir * (layer + 1))      # this layer's states of the stack's [num_layers * ndir, N, H]
             h0l = None if h0 is None else h0[sl].contiguous()
             c0l = None if c0 is None else c0[sl].contiguous()
@@ -345,7 +469,7 @@ class _LSTMStackFunction(torch.autograd.Function):
                              ptr(None if d_cn is None else d_cn[sl].contiguous()), ptr(lens_dev), max_len, ptr(d_g),
                              ptr(d_h0), ptr(d_c0), ptr(d_b), t, n, hidden, _lib.stream_ptr()), name)
             d_w, dx = _layer_products(xl, live if layer == 0 else None, hs, h0l, final, d_g, d_g, [w[0] for w in lw],
-                                        layer > 0 or ctx.needs_input_grad[5])
+                                        layer > 0 or ctx.needs_input_grad[6])
             for d in range(ndir):
                 base = 4 * (ndir * layer + d)
                 w_grads[base], w_grads[base + 1] = d_w[d]
@@ -353,7 +477,8 @@ class _LSTMStackFunction(torch.autograd.Function):
                 w_grads[base + 3] = d_b[d] if lw[d][3] is not None else None
             d_h0s[layer], d_c0s[layer] = d_h0, d_c0
             if dx is not None:
-                d_top = dx
+                # (the gradient handed down a layer passes through the mask the forward put on that layer's output)
+                d_top = dx if (m["drop"] is None or layer == 0) else apply_mask(dx, dx, m["drop"][layer - 1])
         return _stack_grads(ctx, d_top, torch.cat(d_h0s, 0), torch.cat(d_c0s, 0), w_grads)
 
 
@@ -366,12 +491,12 @@ class _GRUStackFunction(torch.autograd.Function):
     gradients are the n-block rows ``[2H:3H]`` of the GRU's, and dx / d_h0 are used as they are."""
 
     @staticmethod
-    def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, x, h0, *flat):
+    def forward(ctx, rnn, lens_dev, max_len, ragged, has_hx, drop, x, h0, *flat):
         ctx.tanh = rnn.rnn_type == RNNType.BASIC_RNN
         ctx.ndir = 2 if rnn.bidirectional else 1
         # (the GRU form of a tanh layer is the cached one the forward itself runs on where that width has a persistent kernel)
         ctx.as_gru = [pk.tanh_as_gru(lp) for pk, lp in zip(rnn._packed, rnn._layer_params())] if ctx.tanh else None
-        return _stack_forward(ctx, ctx.ndir, rnn, lens_dev, max_len, ragged, has_hx, x, h0, None, flat,
+        return _stack_forward(ctx, ctx.ndir, rnn, lens_dev, max_len, ragged, has_hx, drop, x, h0, None, flat,
                               cell=_lib.CELL_RNN_TANH if ctx.tanh else _lib.CELL_GRU)
 
     @staticmethod
@@ -390,11 +515,13 @@ class _GRUStackFunction(torch.autograd.Function):
         d_hn = None if d_hn is None else _lib.f32c(d_hn)
         d_h0s = [None] * nl
         w_grads = [None] * (4 * ndir * nl)
+        scratch = None
         own_rows = slice(2 * hidden, h3) if ctx.tanh else slice(None)
         for layer in range(nl - 1, -1, -1):
             own = [tuple(weights[4 * (ndir * layer + d):4 * (ndir * layer + d) + 4]) for d in range(ndir)]
             lw = ctx.as_gru[layer] if ctx.tanh else own      # per direction (w_ih, w_hh, b_ih, b_hh) of the GRU
-            xl, hs = layer_in[layer], _dir_outputs(layer_in[layer + 1], hidden, ndir)
+            xl, scratch = _layer_input(m, layer_in, layer, scratch)
+            hs = _dir_outputs(layer_in[layer + 1], hidden, ndir)
             sl = slice(ndir * layer, ndir * (layer + 1))      # this layer's states of the stack's [num_layers * ndir, N, H]
             h0l = None if h0 is None else h0[sl].contiguous()
             for d in range(ndir):
@@ -410,7 +537,7 @@ class _GRUStackFunction(torch.autograd.Function):
                                                  ptr(d_gi), ptr(d_gh), ptr(d_h0), ptr(d_bi), ptr(d_bh), t, n, hidden, ndir,
                                                  _lib.stream_ptr()), "ms_gru_backward_steps")
             d_w, dx = _layer_products(xl, live if layer == 0 else None, hs, h0l, final, d_gi, d_gh, [w[0] for w in lw],
-                                        layer > 0 or ctx.needs_input_grad[5])
+                                        layer > 0 or ctx.needs_input_grad[6])
             for d in range(ndir):
                 base = 4 * (ndir * layer + d)
                 w_grads[base], w_grads[base + 1] = d_w[d][0][own_rows], d_w[d][1][own_rows]
@@ -418,7 +545,8 @@ class _GRUStackFunction(torch.autograd.Function):
                 w_grads[base + 3] = d_bh[d][own_rows] if own[d][3] is not None else None
             d_h0s[layer] = d_h0
             if dx is not None:
-                d_top = dx
+                # (the gradient handed down a layer passes through the mask the forward put on that layer's output)
+                d_top = dx if (m["drop"] is None or layer == 0) else apply_mask(dx, dx, m["drop"][layer - 1])
         return _stack_grads(ctx, d_top, torch.cat(d_h0s, 0), None, w_grads)
 
 
@@ -447,36 +575,45 @@ def _checked_lens(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx, single_stat
     return lens_cpu
 
 
-def _stack_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx):
+def _stack_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx, generator, what):
     """The autograd node of an LSTM stack the caller has vetted (``_LSTMStackFunction``)."""
+    if _needs_generator(rnn, generator):
+        raise ValueError(f"{what} does not serve inter-layer dropout in training mode")
     lens_cpu = _checked_lens(rnn, x, lens, hx)
     _lib.require_gpu()
+    drop = _stack_dropout(rnn, generator, what)      # (after the device check: a call that cannot run consumes no offset)
     max_len = int(lens_cpu[0])
     flat = [p for layer in rnn._layer_params() for d in layer for p in d]
     h0, c0 = hx if hx is not None else (None, None)
     out, hn, cn = _LSTMStackFunction.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None,
-                                           x, h0, c0, *flat)
+                                           drop, x, h0, c0, *flat)
     return out, (hn, cn)
 
 
-def rnn_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-              ) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+def _needs_generator(rnn: RNN, generator) -> bool:
+    """Inter-layer dropout is due in this forward and there is no generator to draw its masks from."""
+    return (rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1 and generator is None
+            and rnn.dropout_generator is None)
+
+
+def rnn_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+              generator: Optional[DropoutGenerator] = None) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
     """``lstm_train`` for LSTM stacks of either kind: x [T, N, In] TIME-MAJOR (whatever ``rnn.batch_first`` says:
     ``RNN.forward(differentiable=True)`` does the transposes), lens [N] sorted descending, hx = (h0, c0)
     [num_layers * ndir, N, H] or None (zeros) -> ``(out [T, N, ndir H], (h_n, c_n))`` with ``RNN.forward``'s values,
     differentiable in x, hx and every parameter, the ``_reverse`` ones included.  A unidirectional stack is ``lstm_train``'s
-    node; a bidirectional one runs both directions' backward recurrences in the same launches."""
+    node; a bidirectional one runs both directions' backward recurrences in the same launches.  Inter-layer dropout in training
+    mode draws its masks from ``generator`` or ``rnn.dropout_generator`` (one offset per layer but the last) and is refused
+    with ValueError where neither is there."""
     if not isinstance(rnn, RNN):
         raise ValueError(f"rnn_train serves RNN modules, not {type(rnn).__name__} (HardLSTM has no backward in this project)")
     if rnn.rnn_type != RNNType.LSTM:
         raise ValueError("rnn_train serves LSTM stacks only (GRU and tanh cells have no backward in this project)")
-    if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
-        raise ValueError("rnn_train does not serve inter-layer dropout in training mode")
-    return _stack_train(rnn, x, lens, hx)
+    return _stack_train(rnn, x, lens, hx, generator, "rnn_train")
 
 
-def lstm_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-               ) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+def lstm_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               generator: Optional[DropoutGenerator] = None) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
     """x [T, N, In] time-major, lens [N] sorted descending, hx = (h0, c0) [num_layers, N, H] or None (zeros) ->
     ``(out [T, N, H], (h_n, c_n))`` with ``RNN.forward``'s values (rows past a length are 0, the states are those at
     ``lens[n] - 1``), differentiable in x, hx and every parameter of the stack.  ``RNN.forward`` itself is untouched."""
@@ -484,31 +621,33 @@ def lstm_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[Tuple
         raise ValueError("lstm_train serves LSTM stacks only (GRU and tanh cells have no backward in this project)")
     if rnn.bidirectional:
         raise ValueError("lstm_train does not serve bidirectional=True (rnn_train does)")
-    if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
+    if _needs_generator(rnn, generator):
         raise ValueError("lstm_train does not serve inter-layer dropout in training mode")
     if rnn.batch_first:
         raise ValueError("lstm_train takes time-major input (batch_first=False)")
-    return _stack_train(rnn, x, lens, hx)
+    return _stack_train(rnn, x, lens, hx, generator, "lstm_train")
 
 
-def gru_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[torch.Tensor] = None
-              ) -> Tuple[torch.Tensor, torch.Tensor]:
+def gru_train(rnn: RNN, x: torch.Tensor, lens: torch.Tensor, hx: Optional[torch.Tensor] = None,
+              generator: Optional[DropoutGenerator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``rnn_train`` for GRU and tanh (``RNNType.BASIC_RNN``) stacks of either kind: x [T, N, In] TIME-MAJOR (whatever
     ``rnn.batch_first`` says), lens [N] sorted descending, hx ONE tensor [num_layers * ndir, N, H] or None (zeros) ->
     ``(out [T, N, ndir H], h_n)`` with ``RNN.forward``'s values, differentiable in x, hx and every parameter, the ``_reverse``
     ones included (``_GRUStackFunction``: ``ms_gru_recompute`` / ``ms_gru_backward_steps``).  ``rnn_train`` and ``lstm_train``
     keep refusing these cells -- earlier tests pin that -- so this entry is explicit, and ``RNN.forward(differentiable=True)``
     reaches it only with ``rnn.gru_backward = True``.  ValueError, before a device is needed: LSTM stacks (``rnn_train``
-    serves them), ``HardLSTM``, inter-layer dropout in training mode, bad shapes or lengths."""
+    serves them), ``HardLSTM``, inter-layer dropout in training mode with neither ``generator`` nor ``rnn.dropout_generator``,
+    bad shapes or lengths."""
     if not isinstance(rnn, RNN):
         raise ValueError(f"gru_train serves RNN modules, not {type(rnn).__name__} (HardLSTM has no backward in this project)")
     if rnn.rnn_type == RNNType.LSTM:
         raise ValueError("gru_train serves GRU and tanh stacks; an LSTM stack goes through rnn_train")
-    if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1:
+    if _needs_generator(rnn, generator):
         raise ValueError("gru_train does not serve inter-layer dropout in training mode")
     lens_cpu = _checked_lens(rnn, x, lens, hx, single_state=True)
     _lib.require_gpu()
+    drop = _stack_dropout(rnn, generator, "gru_train")
     max_len = int(lens_cpu[0])
     flat = [p for layer in rnn._layer_params() for d in layer for p in d]
-    return _GRUStackFunction.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None, x, hx,
-                                   *flat)
+    return _GRUStackFunction.apply(rnn, _lib.lens_i32(lens_cpu), max_len, bool(int(lens_cpu[-1]) < max_len), hx is not None, drop, x,
+                                   hx, *flat)

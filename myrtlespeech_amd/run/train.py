@@ -11,9 +11,12 @@ model has an optimizer.
 The one deliberate difference: the TRAIN stage calls ``seq_to_seq.model(x, differentiable=True)`` -- this project's default
 forward is the detached inference path; the EVAL stage calls ``seq_to_seq.model(x)`` under ``torch.no_grad()``.
 
-Limits: the differentiable forwards refuse dropout masks in training mode, so ``fit`` on the shipped DeepSpeech1 configuration
-(``drop_prob: 0.25``) raises that ``ValueError`` at the first training batch; the shipped DeepSpeech2 configuration has no
-dropout and trains once ``model.rnn.gru_backward = True``."""
+Limits: the differentiable forwards serve dropout in training mode only with a source of randomness attached, so ``fit`` on the
+shipped DeepSpeech1 configuration (``drop_prob: 0.25``) needs one line in front of it --
+``dropout.attach(seq_to_seq.model, dropout.DropoutGenerator(seed))`` (``myrtlespeech_amd.model.dropout``) -- and raises the
+forward's ``ValueError`` at the first training batch without it; the masks are a pure function of ``(seed, offset)``, so two runs
+from the same seed end in the same parameters, and the EVAL stages consume no offset.  The shipped DeepSpeech2 configuration has
+no dropout and trains once ``model.rnn.gru_backward = True``.  ``fit`` itself knows nothing of either switch."""
 from typing import Collection, Iterable, Optional
 
 import torch
