@@ -10,6 +10,12 @@ pad_packed_sequence(total_length)``) never reads a padded row and is indifferent
   4. the content of the padding does not matter: 1e4 * randn, then NaN, in every padded frame -- the same bits;
   5. no time-out word is left in the module's workspace.
 
+The other two split modes -- MS_PRECISION=bf16x3 and MS_PRECISION=fp16, read once per process -- run their subsets of the
+lattice (``LC.BF16X3_CHILD``, ``LC.FP16_CHILD``) in one child process each.  Checks 2 to 5 and the stack-against-loop bit
+comparisons are the same and take no tolerance; check 1 holds the device to rtol = atol = max(1e-4, 2 E), E being the distance
+of the operand-rounding emulation (rnn_ref64, ``operands=``) from the same float64 reference, computed in the child from the
+reference side alone (``LC.check_mode_accuracy``).
+
 The cases, their inputs and weights: tests/rnn_length_cases.py (shared with tests/test_rnn_ref64_cpu.py, which shows on the CPU
 that the float32 oracle stays within a quarter of the tolerance of the float64 reference on each of them).  Needs a real
 MI355X: -m gpu."""
@@ -37,15 +43,17 @@ def cpu(t):
     return t.detach().cpu().numpy()
 
 
-def reference(case, x, lens, hx, sd):
-    """-> (out, h_n, c_n | None) float64; only the M steps that exist are computed (the rest of ``out`` is zero by definition)."""
+def reference(case, x, lens, hx, sd, operands=None):
+    """-> (out, h_n, c_n | None) float64; only the M steps that exist are computed (the rest of ``out`` is zero by definition).
+    ``operands``: the emulation of a mode's operand rounding instead of the reference itself (rnn_ref64)."""
     if case.kind == "HARD":
-        out, (hn, cn) = R64.hard_lstm_forward(x, sd, case.H, case.nl, case.bidir, hx)
+        out, (hn, cn) = R64.hard_lstm_forward(x, sd, case.H, case.nl, case.bidir, hx, operands=operands)
         return out, hn, cn
     if case.kind == "LSTM":
-        out, (hn, cn) = R64.rnn_forward(R64.LSTM, x, lens, sd, case.H, case.nl, case.bidir, hx)
+        out, (hn, cn) = R64.rnn_forward(R64.LSTM, x, lens, sd, case.H, case.nl, case.bidir, hx, operands=operands)
         return out, hn, cn
-    out, hn = R64.rnn_forward(R64.GRU if case.kind == "GRU" else R64.RNN_TANH, x, lens, sd, case.H, case.nl, case.bidir, hx)
+    out, hn = R64.rnn_forward(R64.GRU if case.kind == "GRU" else R64.RNN_TANH, x, lens, sd, case.H, case.nl, case.bidir, hx,
+                              operands=operands)
     return out, hn, None
 
 
@@ -125,14 +133,38 @@ def assert_intended_path(case):
             assert (hp, as_gru) == (512, 1), (case.id, hp, as_gru)
     elif case.sched == "S9":
         assert not _lib.split_precision() and p["overlap"] == 0 and p["packs"] == 0, (case.id, p)
+    elif case.sched == "S10":
+        if case.H == 64:        # the one-stream split kernel at its own width: not padded, planes not chained
+            assert (p["padded"], p["chains"], p["wide"]) == (64, 0, 0), (case.id, p)
+        else:                   # the two-stream kernel beyond 1 024 units: chained planes, 8-unit workgroups, never overlapped
+            assert (p["padded"], p["chains"], p["wide"], p["overlap"]) == (case.H, 1, 0, 0), (case.id, p)
     return p
 
 
-def check_case(case):
+def assert_mode_path(case, mode, path):
+    """(in a mode's child) the process runs that mode, and the case reaches the path recorded for it there."""
+    from myrtlespeech_amd import _lib
+    lib = _lib.load()
+    assert os.environ.get("MS_PRECISION") == mode and _lib.split_precision(), mode
+    p = assert_intended_path(case._replace(path=path))
+    if mode == "fp16":          # rows never pack in this mode, whatever the lengths
+        cell, ndir = cell_of(case), 2 if case.bidir else 1
+        for k in (case.In, ndir * case.H):
+            assert lib.ms_rnn_layer_packs_rows(cell, LC.steps_of(case), case.N, k, case.H, ndir) == 0, (case.id, k)
+        assert p["packs"] == 0 and path != "packed", (case.id, p)
+    return p
+
+
+def check_case(case, mode=None, path=None):
+    """``mode`` / ``path`` (a mode's child): the path the case takes in that mode, and check 1 by the mode's criterion."""
     from myrtlespeech_amd import _lib
     from myrtlespeech_amd.model import rnn as R
     lib = _lib.load()
-    assert_intended_path(case)
+    if mode is None:
+        assert_intended_path(case)
+        path = case.path
+    else:
+        assert_mode_path(case, mode, path)
     m, sd = build_module(case)
     x, lens, hx = LC.make_inputs(case)
     xd = T(x).cuda()
@@ -141,7 +173,11 @@ def check_case(case):
     got = forward(m, case, xd, lens_t, hxd)
     M = LC.steps_of(case)
     # 1. against the float64 reference
-    if case.gain == 1.0:
+    if case.gain == 1.0 and mode is not None:
+        want = reference(case, x[:M], lens, hx, sd)
+        dev = tuple(None if a is None else cpu(a) for a in got)
+        LC.check_mode_accuracy(case, mode, (dev[0][:M],) + dev[1:], want, reference(case, x[:M], lens, hx, sd, mode))
+    elif case.gain == 1.0:
         want = reference(case, x[:M], lens, hx, sd)
         for name, a, b in zip(("out", "h_n", "c_n"), got, want):
             if b is None:
@@ -151,7 +187,7 @@ def check_case(case):
                 a = a[:M]
             print(case.id, name, "max |kernel - f64| =", float(np.abs(a - b).max()), "max |f64| =", float(np.abs(b).max()))
             np.testing.assert_allclose(a, b, err_msg=f"{case.id} {name}", **TOL)
-    if case.path == "overlap":      # ... and the layer loop's bits
+    if path == "overlap":           # ... and the layer loop's bits
         prev = R._OVERLAP
         R._OVERLAP = False
         try:
@@ -233,6 +269,26 @@ def run_f32_cases():
     for case in LC.F32_CHILD:
         check_case(case)
     print("f32 lengths ok", len(LC.F32_CHILD))
+
+
+def run_mode_cases(mode):
+    """(in a child process started with MS_PRECISION=<mode>) every case of the mode's subset; the first failure ends the child."""
+    cases = LC.MODE_CHILD[mode]
+    for cid, path in cases:
+        check_case(LC.BY_ID[cid], mode, path)
+    print(f"{mode} lengths ok", len(cases))
+
+
+@pytest.mark.parametrize("mode", sorted(LC.MODE_CHILD))
+def test_split_mode_lengths_in_subprocess(mode):
+    """MS_PRECISION=bf16x3 / fp16: the mode's subset of the lattice in one fresh child, once, under its own time limit."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import test_gpu_rnn_lengths as G; G.run_mode_cases(%r)\n") % (root, os.path.join(root, "tests"), mode)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MS_PRECISION=mode), capture_output=True, text=True,
+                       timeout=600)
+    print(r.stdout[-20000:])      # E, the device's distance and their ratio, per case and quantity
+    assert r.returncode == 0 and f"{mode} lengths ok {len(LC.MODE_CHILD[mode])}" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
 
 
 def test_exact_f32_mode_lengths_in_subprocess():
