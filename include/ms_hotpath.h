@@ -703,6 +703,11 @@ int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const float* embeddi
                    const float* w_out, const float* b_out, int32_t* out_idx, int32_t* out_len, float* out_score, int T,
                    int N, int V, int D, int H, int L, int J, int beam_width, int max_symbols, int greedy, void* workspace,
                    size_t workspace_bytes, void* stream);
+/* Greedy iterations (joint of 32 frames per utterance, scan, predictor step) that the calling thread's last ms_rnnt_decode
+ * enqueued; 0 after a beam call, a refused call or no call at all.  A record for tools and tests, like word [1] of the
+ * streaming state below: an utterance is finished once its frame reaches its length (one of length <= 0 from the start), and
+ * the host, which looks every second iteration at a counter fetched two looks earlier, stops within six iterations of that. */
+long long ms_rnnt_decode_last_iterations(void);
 
 /* The greedy decode advanced one chunk of encoder rows at a time (own specification: oracle/rnnt_oracle.py::greedy_decode
  * with its frame loop cut BETWEEN frames; restated in numpy by tests/rnnt_stream_ref.py).  The predictor's LSTM state and the

@@ -113,6 +113,7 @@ SIGNATURES = {
                                       c_int, c_int, _P, c_int, _P, _P, _P, _P, c_size_t, _P, _P, _P, c_size_t, c_int, _P, _P]),
     "ms_rnnt_decode_workspace_bytes": (c_size_t, [c_int] * 10),
     "ms_rnnt_decode": (c_int, [_P, _P, _P, _PP, _PP, _PP, _PP, _P, _P, _P, _P, _P, _P] + [c_int] * 10 + [_P, c_size_t, _P]),
+    "ms_rnnt_decode_last_iterations": (ctypes.c_longlong, []),
     "ms_rnnt_greedy_stream_state_bytes": (c_size_t, [c_int] * 4),
     "ms_rnnt_greedy_stream_workspace_bytes": (c_size_t, [c_int] * 6),
     "ms_rnnt_greedy_stream_begin": (c_int, [_P, c_int, _P, _PP, _PP, _PP, _PP, _P, _P, _P] + [c_int] * 5 + [_P, c_size_t, _P]),

@@ -897,11 +897,15 @@ __global__ void beam_init_kernel(BeamP p) {
 
 // ---- greedy -----------------------------------------------------------------------------------------------------
 
+// (done_cnt is zero at the launch.  An utterance without frames is finished from the start: the scan leaves at `t0 >= len`
+// before it counts anything, so it is counted here -- once, the scan never reaches its count -- or the host's poll would wait
+// for it through all T * max_symbols iterations.)
 __global__ void greedy_init_kernel(int32_t* ext_label, int32_t* ext_src, int32_t* ext_dst, int32_t* slot, int32_t* out_cnt,
-                                   int32_t* cur_t, int32_t* sym, int32_t* done_cnt, int N, int blank) {
+                                   int32_t* cur_t, int32_t* sym, int32_t* done_cnt, const int32_t* __restrict__ lens, int N,
+                                   int blank) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) *done_cnt = 0;
   if (i >= N) return;
+  if (lens[i] <= 0) atomicAdd(done_cnt, 1);
   ext_label[i] = blank;
   ext_src[i] = -1;
   ext_dst[i] = i;
@@ -1608,7 +1612,12 @@ int beam2_decode(const BeamP& p, const Net& n, const DecLayout& W, char* ws, con
                : beam2_frames<2, false>(p, n, W, ws, enc_p, out_idx, out_len, out_score, T, max_symbols, s);
 }
 
+// iterations the calling thread's last greedy decode enqueued (ms_rnnt_decode_last_iterations)
+thread_local long long g_last_greedy_iters = 0;
+
 }  // namespace
+
+extern "C" long long ms_rnnt_decode_last_iterations(void) { return g_last_greedy_iters; }
 
 extern "C" size_t ms_rnnt_decode_workspace_bytes(int T, int N, int V, int D, int H, int L, int J, int beam_width,
                                                  int max_symbols, int greedy) {
@@ -1623,6 +1632,7 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
                               int32_t* out_len, float* out_score, int T, int N, int V, int D, int H, int L, int J,
                               int beam_width, int max_symbols, int greedy, void* workspace, size_t workspace_bytes,
                               void* stream) {
+  g_last_greedy_iters = 0;
   MS_REQUIRE(enc_p && lens && embedding && w_ih && w_hh && b_ih && b_hh && w_pred && w_out && out_idx && out_len && workspace,
              "null pointer");
   MS_REQUIRE(T > 0 && N > 0 && V > 0 && D > 0 && H > 0 && L > 0 && L <= 8 && J > 0 && max_symbols > 0, "bad shape");
@@ -1661,8 +1671,9 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
     int32_t* done_cnt = (int32_t*)(ws + W.B_cnt);      // utterances that have reached their length
     int32_t* out_cnt = (int32_t*)(ws + W.out_cnt);
     const int out_stride = T * max_symbols;
+    MS_HIP(hipMemsetAsync(done_cnt, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(greedy_init_kernel, dim3(ms::cdiv(N, 64)), dim3(64), 0, s, (int32_t*)(ws + W.ext_label),
-                       (int32_t*)(ws + W.ext_src), (int32_t*)(ws + W.ext_dst), A_slot, out_cnt, cur_t, sym, done_cnt, N, V);
+                       (int32_t*)(ws + W.ext_src), (int32_t*)(ws + W.ext_dst), A_slot, out_cnt, cur_t, sym, done_cnt, lens, N, V);
     MS_LAUNCH_CHECK();
     int rc = predictor_step(net, W, ws, s);
     if (rc != MS_OK) return rc;
@@ -1690,6 +1701,7 @@ extern "C" int ms_rnnt_decode(const float* enc_p, const int32_t* lens, const flo
       hipLaunchKernelGGL(greedy_scan_kernel, dim3(N), dim3(64), 0, s, logp, lens, cur_t, sym, done_cnt, out_idx, out_cnt,
                          (int32_t*)(ws + W.ext_label), (int32_t*)(ws + W.ext_src), (int32_t*)(ws + W.ext_dst), V1, V, out_stride,
                          max_symbols);
+      ++g_last_greedy_iters;
       if (hipGetLastError() != hipSuccess) { ms::set_error("ms_rnnt_decode: launch failed"); rc = MS_ERR_HIP; break; }
       rc = predictor_step(net, W, ws, s);
       if (rc != MS_OK || (it + 1) % CHECK_EVERY != 0) continue;
