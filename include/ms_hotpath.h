@@ -1104,6 +1104,53 @@ int ms_gru_backward_steps(const float* gates, const float* q, const float* h, co
                           float* dGi, float* dGh, float* d_h0, float* d_b_ih, float* d_b_hh, int T, int N, int H, int ndir,
                           void* stream);
 
+/* ---- HardLSTM backward through time (csrc/rnn_backward.hip): what lets a loss reach DeepSpeech1(hard_lstm=True).
+ *      OWN specification; restated in float64 numpy by tests/hard_lstm_backward_ref.py.
+ *
+ * One direction of one HardLSTM layer (model/hard_lstm.py: hard sigmoid, hard tanh), float32 throughout, weights in torch
+ * layout and read as stored: w_ih [4H, In], w_hh [4H, H], b_ih / b_hh [4H] or NULL (zeros), gate order i, f, g, o.  HardLSTM
+ * ignores sequence lengths: every sequence has T steps and neither call takes lens.
+ *   a   = x_t w_ih^T + b_ih + h_prev w_hh^T + b_hh
+ *   z_k = fl(fl(0.2f a_k) + 0.5f)   k in {i, f, o}      TWO roundings, never a fused multiply-add
+ *   i, f, o = min(max(z_k, 0), 1);   g = min(max(a_g, -1), 1)
+ *   c_t = f c_prev + i g;   h_t = o min(max(c_t, -1), 1)
+ * The two-rounding clause: the forward kernels form 0.2f a + 0.5f fused, which gives the same value AFTER the clamp, but the
+ * derivative is discontinuous in z and its gate is decided on z itself.  At a = -2.5 the fused form is -7.45e-9 (outside) where
+ * the reference's two torch ops give exactly 0 (inside: torch.clamp passes the gradient on the closed interval).  The
+ * backward follows the reference, so the recompute rounds twice.
+ * Gradient gates, the reference's ops under torch autograd, both selects (never a multiply by 0 or 1; a NaN compares false):
+ *   P(z) = 1 iff 0 <= z <= 1      torch.clamp: closed
+ *   Q(v) = 1 iff -1 < v < 1       torch.nn.Hardtanh: open
+ * Backward, direction 0, for t = T - 1 down to 0 (the reverse direction mirrors it from t = 0 up to T - 1, as in the LSTM block):
+ *   dh_t = d_out[t] + dA_{t+1} w_hh                 (+ d_hn at the last step; no recurrent term there)
+ *   dc_t = dh_t o Q(c_t) + f_{t+1} dc_{t+1}         (d_cn in place of the carried term at the last step)
+ *   dA_t = [0.2 dc_t g P(z_i),  0.2 dc_t c_prev P(z_f),  dc_t i Q(a_g),  0.2 dh_t clamp11(c_t) P(z_o)]
+ *   d_h0 = dA_first w_hh;   d_c0 = f_first dc_first;   d_b = the column sums of dA
+ * each product rounded on its own in autograd's order ((dc g), the select, then the 0.2), so that on inputs whose forward
+ * values are exact dA, d_c0 and d_b are torch float32 autograd's bits.
+ *
+ * ms_hard_lstm_recompute.  ms_lstm_recompute_dir's two batch products (the same workspace:
+ * ms_lstm_recompute_workspace_bytes) and a scan that writes gates [T,N,4H] = the PRE-CLAMP values z_i, z_f, a_g, z_o -- not the
+ * activated gates: a gate of exactly 0 may come from z == 0, which passes a gradient, or from z < 0, which does not, so the
+ * backward derives both the value and the gate from z; the memory is the soft entry's -- and c [T,N,H], unclamped.
+ *
+ * ms_hard_lstm_backward_steps.  ndir is 1 or 2.  gates [ndir,T,N,4H] and c [ndir,T,N,H] direction major (the recompute's
+ * results), c0 / d_hn / d_cn [ndir,N,H] or NULL, w_hh_rev NULL when ndir == 1, d_out [T,N,ndir H] read in place (direction d at
+ * column d H + j).  Outputs, always fully written: dA [ndir,T,N,4H] (16-byte aligned), d_h0 and d_c0 [ndir,N,H] (d_c0 also
+ * carries dc between the launches), d_b [ndir,4H].  T + 1 launches of the step kernel of ms_lstm_backward_steps on a
+ * (ceil(H / 32), ndir) grid with a third cell policy, and every promise of that block: stream order only, no atomics, float32
+ * MFMA over K = 4H, the same bits on every run; direction 0 of an ndir == 2 call is the ndir == 1 call's bits.
+ *
+ * Errors: NULL pointers (other than the optional ones above), non-positive shapes, reverse outside {0, 1}, ndir outside
+ * {1, 2} MS_ERR_INVALID; a short workspace MS_ERR_WORKSPACE.  Out of scope: a single-launch recurrence, a K-split of the step
+ * product, mixed precision, dropout inside HardLSTM (the reference asserts there is none). */
+int ms_hard_lstm_recompute(const float* x, const float* h, const float* h0, const float* c0, const float* w_ih,
+                           const float* w_hh, const float* b_ih, const float* b_hh, float* gates, float* c, int T, int N, int In,
+                           int H, int reverse, void* workspace, size_t workspace_bytes, void* stream);
+int ms_hard_lstm_backward_steps(const float* gates, const float* c, const float* c0, const float* w_hh_fwd,
+                                const float* w_hh_rev, const float* d_out, const float* d_hn, const float* d_cn, float* dA,
+                                float* d_h0, float* d_c0, float* d_b, int T, int N, int H, int ndir, void* stream);
+
 /* ---- training: convolution and lookahead backward (csrc/conv_backward.hip) -- OWN specification ---------------------
  *
  * The forward is ms_maskconv_forward's contract with groups == 1:

@@ -141,6 +141,8 @@ SIGNATURES = {
     "ms_lstm_recompute_dir": (c_int, [_P] * 11 + [c_int] * 5 + [_P, c_size_t, _P]),
     "ms_lstm_backward_steps_bidir": (c_int, [_P] * 9 + [c_int] + [_P] * 4 + [c_int] * 3 + [_P]),
     "ms_embedding_backward": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "ms_hard_lstm_recompute": (c_int, [_P] * 10 + [c_int] * 5 + [_P, c_size_t, _P]),
+    "ms_hard_lstm_backward_steps": (c_int, [_P] * 12 + [c_int] * 4 + [_P]),
     "ms_gru_recompute_workspace_bytes": (c_size_t, [c_int] * 3),
     "ms_gru_recompute": (c_int, [_P] * 10 + [c_int] * 5 + [_P, c_size_t, _P]),
     "ms_gru_backward_steps": (c_int, [_P] * 9 + [c_int] + [_P] * 5 + [c_int] * 4 + [_P]),

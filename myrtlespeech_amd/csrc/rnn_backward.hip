@@ -16,7 +16,9 @@
 // The product dh = dG_prev w_hh (K = G H, G = 4 or 3 gates) runs on v_mfma_f32_32x32x2_f32: gate gradients sit below fp16's
 // normal range, where the hi + lo planes used elsewhere lose what the split exists to keep.  w_hh [G H, H] is contiguous in j,
 // so a wave's B operand is 32 consecutive floats of a row, read as stored.  The kernel is one template around a cell policy
-// (LstmCell, GruCell): the policy holds the cell's arithmetic and its argument block, the template everything else.
+// (LstmCell, GruCell, HardLstmCell): the policy holds the cell's arithmetic and its argument block, the template everything else.
+// ms_hard_lstm_recompute / ms_hard_lstm_backward_steps are HardLSTM's pair (hard sigmoid / hard tanh, no lengths): the same
+// products, a scan that keeps the PRE-CLAMP gate values, and the step kernel around HardLstmCell (tests/hard_lstm_backward_ref.py).
 #include "common.h"
 
 namespace ms {
@@ -91,6 +93,48 @@ __global__ __launch_bounds__(256) void lstm_scan_kernel(const float* __restrict_
     gates[base + (size_t)H] = gf;
     gates[base + (size_t)2 * H] = gg;
     gates[base + (size_t)3 * H] = go;
+    c[((size_t)t * N + n) * H + j] = cc;
+    cprev = cc;
+  }
+}
+
+// The hard cell's pre-clamp gate value fl(fl(0.2f a) + 0.5f): TWO roundings, as the reference's two torch ops make them.  Two
+// statements, so the build (which contracts inside one expression only) cannot fuse them: at a = -2.5 the fused form is
+// -7.45e-9, outside the clamp, where the two-op form is exactly 0, inside it -- and the backward's gate is decided there.
+__device__ __forceinline__ float hard_pre(float a) {
+  const float m = 0.2f * a;
+  return m + 0.5f;
+}
+
+// The hard cell (HardLSTM: no lengths, every sequence has T steps).  gates [T,N,4H] holds the PRE-CLAMP values z_i, z_f, a_g, z_o
+// -- the activated gate does not say whether a 0 came from exactly 0 (gradient passes) or from below (it does not) -- and c
+// [T,N,H] the unclamped cell state.  Steps in the direction's own order, the first one visited takes p2's `h0_row`.
+__global__ __launch_bounds__(256) void hard_lstm_scan_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                             const float* __restrict__ b_hh, const float* __restrict__ c0,
+                                                             float* __restrict__ gates, float* __restrict__ c, int T, int N, int H,
+                                                             int have_h0, int reverse) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)N * H) return;
+  const int n = (int)(idx / H), j = (int)(idx % H);
+  const int h0_row = reverse ? T - 1 : 0;
+  float cprev = c0 ? c0[idx] : 0.f;
+  for (int s = 0; s < T; ++s) {
+    const int t = reverse ? T - 1 - s : s;
+    const size_t base = ((size_t)t * N + n) * 4 * H + j;
+    const size_t rbase = ((size_t)(s == 0 ? h0_row : t) * N + n) * 4 * H + j;
+    float pre[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      // (first step from a zero state: the recurrent product is 0 and only its bias remains)
+      const float rec = (s == 0 && !have_h0) ? (b_hh ? b_hh[g * H + j] : 0.f) : p2[rbase + (size_t)g * H];
+      pre[g] = p1[base + (size_t)g * H] + rec;
+    }
+    const float zi = hard_pre(pre[0]), zf = hard_pre(pre[1]), ag = pre[2], zo = hard_pre(pre[3]);
+    const float cc = act_clamp(zf, 0.f, 1.f) * cprev + act_clamp(zi, 0.f, 1.f) * act_clamp(ag, -1.f, 1.f);
+    gates[base] = zi;
+    gates[base + (size_t)H] = zf;
+    gates[base + (size_t)2 * H] = ag;
+    gates[base + (size_t)3 * H] = zo;
     c[((size_t)t * N + n) * H + j] = cc;
     cprev = cc;
   }
@@ -210,6 +254,55 @@ struct LstmCell {
   __device__ __forceinline__ static void store_sum(const Dir& d, int g, size_t u, int H, float s, int first) {
     const size_t o = (size_t)g * H + u;
     d.d_b[o] = first ? s : d.d_b[o] + s;
+  }
+};
+
+// The hard cell against the LSTM: `gates` holds the pre-clamp values (hard_lstm_scan_kernel), from which both the gate's value
+// and its derivative's gate come.  P (torch.clamp: the CLOSED interval passes) and Q (torch.nn.Hardtanh: the OPEN one) are
+// selects, never multiplies by 0 or 1, and a NaN compares false.  The statements follow torch autograd's own operations one
+// rounding each -- a product, the select, then the hard sigmoid's 0.2 -- so nothing here is contracted.
+struct HardLstmCell : LstmCell {
+  __device__ __forceinline__ static void live_row(const Dir& d, float dh, bool last, int len, size_t grow, size_t tnj, size_t nj,
+                                                  int N, int H, float (&bsum)[4]) {
+    const float* __restrict__ gates = d.gates;
+    const float* __restrict__ c = d.c;
+    const float* __restrict__ c0 = d.c0;
+    const float* __restrict__ d_hn = d.d_hn;
+    const float* __restrict__ d_cn = d.d_cn;
+    float* __restrict__ dG = d.dgh;
+    float* __restrict__ dc_buf = d.dc_buf;
+    const int t = d.t;
+    if (last && d_hn) dh += d_hn[nj];
+    float dc = last ? (d_cn ? d_cn[nj] : 0.f) : dc_buf[nj];
+    const float zi = gates[grow], zf = gates[grow + (size_t)H], ag = gates[grow + (size_t)2 * H], zo = gates[grow + (size_t)3 * H];
+    float cprev;
+    if (d.reverse) cprev = t + 1 < len ? c[tnj + (size_t)N * H] : (c0 ? c0[nj] : 0.f);
+    else cprev = t > 0 ? c[tnj - (size_t)N * H] : (c0 ? c0[nj] : 0.f);
+    const float cc = c[tnj];
+    const float gi = act_clamp(zi, 0.f, 1.f), gf = act_clamp(zf, 0.f, 1.f), gg = act_clamp(ag, -1.f, 1.f);
+    const float go = act_clamp(zo, 0.f, 1.f), tc = act_clamp(cc, -1.f, 1.f);
+    const bool p_i = zi >= 0.f && zi <= 1.f, p_f = zf >= 0.f && zf <= 1.f, p_o = zo >= 0.f && zo <= 1.f;
+    const bool q_g = ag > -1.f && ag < 1.f, q_c = cc > -1.f && cc < 1.f;
+    const float dtc = dh * go;
+    const float dcs = q_c ? dtc : 0.f;
+    dc = dc + dcs;
+    const float di = dc * gg;
+    const float df = dc * cprev;
+    const float dg = dc * gi;
+    const float dO = dh * tc;
+    const float dgi = p_i ? di * 0.2f : 0.f;
+    const float dgf = p_f ? df * 0.2f : 0.f;
+    const float dgg = q_g ? dg : 0.f;
+    const float dgo = p_o ? dO * 0.2f : 0.f;
+    dc_buf[nj] = dc * gf;
+    dG[grow] = dgi;
+    dG[grow + (size_t)H] = dgf;
+    dG[grow + (size_t)2 * H] = dgg;
+    dG[grow + (size_t)3 * H] = dgo;
+    bsum[0] += dgi;
+    bsum[1] += dgf;
+    bsum[2] += dgg;
+    bsum[3] += dgo;
   }
 };
 
@@ -431,13 +524,15 @@ static void bwd_steps_launch(RbStep<Cell>& step, int ndir, const int32_t* lens, 
   }
 }
 
-// ms_lstm_backward_steps (ndir == 1, w_hh_rev unused) and ms_lstm_backward_steps_bidir: direction-major arguments.
+// ms_lstm_backward_steps (ndir == 1, w_hh_rev unused), ms_lstm_backward_steps_bidir and (Cell = HardLstmCell)
+// ms_hard_lstm_backward_steps: direction-major arguments.
+template <class Cell>
 static void lstm_bwd_steps(int ndir, const float* gates, const float* c, const float* c0, const float* w_hh_fwd,
                            const float* w_hh_rev, const float* d_out, const float* d_hn, const float* d_cn, const int32_t* lens,
                            int max_len, float* dG, float* d_h0, float* d_c0, float* d_b, int T, int N, int H, hipStream_t st) {
   const size_t nh = (size_t)N * H;
   const size_t plane = (size_t)T * N * 4 * H;      // one direction of gates / dG; c is plane / 4
-  RbStep<LstmCell> step = {};
+  RbStep<Cell> step = {};
   step.dir[0] = LstmCell::Dir{{gates, w_hh_fwd, d_out, d_hn, nullptr, dG, d_h0, 0, 0, 1}, c, c0, d_cn, d_c0, d_b};
   if (ndir == 2) {
     step.dir[1] = LstmCell::Dir{{gates + plane, w_hh_rev, d_out + H, d_hn ? d_hn + nh : nullptr, nullptr, dG + plane, d_h0 + nh, 0, 1, 1},
@@ -497,7 +592,8 @@ extern "C" int ms_lstm_backward_steps(const float* gates, const float* c, const 
   hipStream_t st = (hipStream_t)stream_;
   const size_t row = (size_t)N * 4 * H;
   if (max_len < T) MS_HIP(hipMemsetAsync(dG + (size_t)max_len * row, 0, (size_t)(T - max_len) * row * sizeof(float), st));
-  ms::lstm_bwd_steps(1, gates, c, c0, w_hh, nullptr, d_out, d_hn, d_cn, lens, max_len, dG, d_h0, d_c0, d_b, T, N, H, st);
+  ms::lstm_bwd_steps<ms::LstmCell>(1, gates, c, c0, w_hh, nullptr, d_out, d_hn, d_cn, lens, max_len, dG, d_h0, d_c0, d_b, T, N, H,
+                                   st);
   MS_LAUNCH_CHECK();
   return MS_OK;
 }
@@ -520,7 +616,50 @@ extern "C" int ms_lstm_backward_steps_bidir(const float* gates, const float* c, 
     MS_HIP(hipMemsetAsync(dG + (size_t)max_len * row, 0, bytes, st));
     MS_HIP(hipMemsetAsync(dG_rev + (size_t)max_len * row, 0, bytes, st));
   }
-  ms::lstm_bwd_steps(2, gates, c, c0, w_hh_fwd, w_hh_rev, d_out, d_hn, d_cn, lens, max_len, dG, d_h0, d_c0, d_b, T, N, H, st);
+  ms::lstm_bwd_steps<ms::LstmCell>(2, gates, c, c0, w_hh_fwd, w_hh_rev, d_out, d_hn, d_cn, lens, max_len, dG, d_h0, d_c0, d_b, T, N,
+                                   H, st);
+  MS_LAUNCH_CHECK();
+  return MS_OK;
+}
+
+extern "C" int ms_hard_lstm_recompute(const float* x, const float* h, const float* h0, const float* c0, const float* w_ih,
+                                      const float* w_hh, const float* b_ih, const float* b_hh, float* gates, float* c, int T, int N,
+                                      int In, int H, int reverse, void* workspace, size_t workspace_bytes, void* stream_) {
+  MS_REQUIRE(x && h && w_ih && w_hh && gates && c, "null pointer");
+  MS_REQUIRE(T > 0 && N > 0 && In > 0 && H > 0, "bad shape");
+  MS_REQUIRE(reverse == 0 || reverse == 1, "reverse must be 0 or 1");
+  MS_REQUIRE((size_t)T * N < ((size_t)1 << 31) / 4 / (size_t)H, "T N 4H exceeds the GEMM's int extents");
+  MS_REQUIRE(workspace != nullptr, "null workspace");
+  if (workspace_bytes < ms_lstm_recompute_workspace_bytes(T, N, H)) {
+    ms::set_error("ms_hard_lstm_recompute: workspace too small");
+    return MS_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream_;
+  float* p1 = (float*)workspace;
+  float* p2 = p1 + ms::recompute_plane_bytes(4, T, N, H) / sizeof(float);
+  const int rc = ms::recompute_products(4, x, h, h0, w_ih, w_hh, b_ih, b_hh, T, N, In, H, reverse, p1, p2, st);
+  if (rc != MS_OK) return rc;
+  const size_t cells = (size_t)N * H;
+  hipLaunchKernelGGL(ms::hard_lstm_scan_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, p1, p2, b_hh, c0, gates, c,
+                     T, N, H, h0 != nullptr ? 1 : 0, reverse);
+  MS_LAUNCH_CHECK();
+  return MS_OK;
+}
+
+extern "C" int ms_hard_lstm_backward_steps(const float* gates, const float* c, const float* c0, const float* w_hh_fwd,
+                                           const float* w_hh_rev, const float* d_out, const float* d_hn, const float* d_cn, float* dA,
+                                           float* d_h0, float* d_c0, float* d_b, int T, int N, int H, int ndir, void* stream_) {
+  MS_REQUIRE(ndir == 1 || ndir == 2, "ndir must be 1 or 2");
+  MS_REQUIRE(gates && c && w_hh_fwd && d_out && dA && d_h0 && d_c0 && d_b, "null pointer");
+  MS_REQUIRE(ndir == 1 || w_hh_rev != nullptr, "null w_hh_rev with ndir == 2");
+  MS_REQUIRE(T > 0 && N > 0 && H > 0, "bad shape");
+  MS_REQUIRE((size_t)T * N < ((size_t)1 << 31) / 4 / (size_t)H, "T N 4H exceeds the int extents");
+  // (both halves of dA are read in 16-byte quads: T N 4H floats apart, so one test covers them)
+  MS_REQUIRE(((uintptr_t)dA & 15) == 0, "dA must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream_;
+  // (no lengths: every sequence has T steps, so no row of dA is left to a memset)
+  ms::lstm_bwd_steps<ms::HardLstmCell>(ndir, gates, c, c0, w_hh_fwd, w_hh_rev, d_out, d_hn, d_cn, nullptr, T, dA, d_h0, d_c0, d_b, T, N,
+                                       H, st);
   MS_LAUNCH_CHECK();
   return MS_OK;
 }

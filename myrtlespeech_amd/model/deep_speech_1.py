@@ -59,8 +59,10 @@ class DeepSpeech1(torch.nn.Module):
         fc1 .. fc4 are ``linear_clamp_dropout_train`` (masks over the time-major [T N, units] outputs, offsets in layer
         order)."""
         from myrtlespeech_amd.model.rnn_autograd import linear_clamp_dropout_train, linear_clamp_train, linear_train
-        if isinstance(self.bi_lstm, HardLSTM):
-            raise ValueError("DeepSpeech1.forward(differentiable=True) does not serve hard_lstm=True (HardLSTM has no backward)")
+        # (the hard cell's backward is opt-in, as RNN.gru_backward is: earlier tests pin the refusal)
+        if isinstance(self.bi_lstm, HardLSTM) and not self.bi_lstm.hard_backward:
+            raise ValueError("DeepSpeech1.forward(differentiable=True) does not serve hard_lstm=True (HardLSTM has no backward "
+                             "unless model.bi_lstm.hard_backward = True)")
         gen = self.dropout_generator if (self.training and self._drop_prob > 0) else None
         if self.training and self._drop_prob > 0 and gen is None:
             raise ValueError("DeepSpeech1.forward(differentiable=True) does not serve dropout masks: train in .eval() or with "
@@ -95,7 +97,7 @@ class DeepSpeech1(torch.nn.Module):
 
         ``differentiable=True``: the same chain and the same structure as autograd nodes on the device, so
         ``CTCLoss()((out, lens), (y, y_lens)).backward()`` fills the gradient of every parameter; ValueError for
-        ``hard_lstm=True``, and for ``drop_prob > 0`` in training mode unless a ``DropoutGenerator`` is attached
+        ``hard_lstm=True`` unless ``self.bi_lstm.hard_backward = True`` (``hard_lstm_train``), and for ``drop_prob > 0`` in training mode unless a ``DropoutGenerator`` is attached
         (``model/dropout.py``: ``attach(model, DropoutGenerator(seed))``).  The default path is untouched."""
         if differentiable:
             return self._forward_train(x, hx)

@@ -105,8 +105,8 @@ class DeepSpeech2(torch.nn.Module):
         """``differentiable=True``: the same chain as autograd nodes on the device (``model/conv_autograd.py``,
         ``model/rnn_autograd.py``), so ``CTCLoss()((out, lens), (y, y_lens)).backward()`` fills the gradient of every parameter
         and of ``hx``; the input features are data and get none.  ValueError, before a device is needed, for what has no
-        backward here: ``HardLSTM`` stacks, GRU / tanh stacks unless ``self.rnn.gru_backward = True`` (the opt-in switch of
-        ``RNN``: fine-tuning the shipped GRU configuration is that one line), dropout in training mode with no ``DropoutGenerator``
+        backward here: ``HardLSTM`` stacks unless ``self.rnn.hard_backward = True``, GRU / tanh stacks unless
+        ``self.rnn.gru_backward = True`` (the opt-in switch of ``RNN``: fine-tuning the shipped GRU configuration is that one line), dropout in training mode with no ``DropoutGenerator``
         attached (``model/dropout.py``: ``attach(model, generator)`` sets ``self.dropout_generator``, which serves the
         ``FullyConnected``'s ``Dropout`` modules, and ``self.rnn.dropout_generator``, which serves the inter-layer dropout; the
         recurrent stack takes its offsets first), ``groups > 1``, and a ``cnn`` or ``lookahead`` holding modules other than the
@@ -117,16 +117,19 @@ class DeepSpeech2(torch.nn.Module):
 
     def _train_plan(self):
         """The differentiable chain, vetted without a device: ([(conv, clamp) | view module, ...], (Lookahead, clamp) | None)."""
+        from myrtlespeech_amd.model.hard_lstm import HardLSTM
         from myrtlespeech_amd.model.rnn import RNN, RNNType
         what = "DeepSpeech2.forward(differentiable=True)"
         rnn, fc = self.rnn, self.fully_connected
-        # (GRU and tanh stacks pass with the stack's opt-in switch on: RNN.forward then sends them to gru_train)
-        if not isinstance(rnn, RNN) or (rnn.rnn_type != RNNType.LSTM and not rnn.gru_backward):
+        # (GRU and tanh stacks pass with the stack's opt-in switch on: RNN.forward then sends them to gru_train; a HardLSTM
+        # with its own, ``hard_backward``: HardLSTM.forward sends it to hard_lstm_train -- it has no dropout to vet)
+        hard = isinstance(rnn, HardLSTM) and rnn.hard_backward
+        if not hard and (not isinstance(rnn, RNN) or (rnn.rnn_type != RNNType.LSTM and not rnn.gru_backward)):
             raise ValueError(f"{what} serves LSTM stacks only (GRU and tanh cells and HardLSTM have no backward in this project)")
         if rnn.batch_first:
             raise ValueError(f"{what} takes a time-major recurrent stack (batch_first=False), as the builder makes it")
         # (dropout is opt-in: served where a DropoutGenerator is attached -- model/dropout.py -- and refused as ever where not)
-        if rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1 and rnn.dropout_generator is None:
+        if not hard and rnn.training and rnn.rnn.dropout > 0 and rnn.rnn.num_layers > 1 and rnn.dropout_generator is None:
             raise ValueError(f"{what} does not serve inter-layer dropout in training mode")
         if not isinstance(fc, FullyConnected):
             raise ValueError(f"{what} serves the builder's FullyConnected, not {type(fc).__name__}")

@@ -5,6 +5,10 @@ Same constructor, I/O contract and state_dict keys
 reference's TorchScript implementation; the per-timestep matmul/cat loop
 (hard_lstm.py:346-379) is replaced by the same HIP kernels as ``RNN`` with the
 hard-activation epilogue.  Sequence lengths are ignored (hard_lstm.py:36).
+
+``forward(..., differentiable=True)`` is the same forward as an autograd node on the device
+(``rnn_autograd.hard_lstm_train``).  The models reach it only with the instance attribute
+``hard_backward = True``: their refusal of a HardLSTM is pinned by earlier tests and stays the default.
 """
 import math
 from typing import Optional, Tuple
@@ -59,6 +63,8 @@ class StackedLSTM(torch.nn.Module):
     def __init__(self, input_size: int, hidden_size: int, num_layers: int, bidirectional: bool,
                  forget_gate_bias: Optional[float]):
         super().__init__()
+        self.hidden_size = hidden_size
+        self.num_layers = num_layers
         layer_type = HardLSTMBidirLayer if bidirectional else HardLSTMLayer
         d = 2 if bidirectional else 1
         self.layers = torch.nn.ModuleList(
@@ -83,6 +89,8 @@ class HardLSTM(torch.nn.Module):
         self._packed = [PackedLayer() for _ in range(num_layers)]
         self._workspace = _lib.Workspace()
         self.check_status = True
+        # opt-in: DeepSpeech1 / DeepSpeech2 ``forward(differentiable=True)`` serve this stack only when it is True
+        self.hard_backward = False
         self.use_cuda = torch.cuda.is_available()
         if self.use_cuda:
             self.rnn = self.rnn.cuda()
@@ -94,8 +102,15 @@ class HardLSTM(torch.nn.Module):
             out.append([(c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh) for c in cells])
         return out
 
-    def forward(self, x: Tuple[Tensor, Tensor], hx: Optional[Tuple[Tensor, Tensor]] = None
+    def forward(self, x: Tuple[Tensor, Tensor], hx: Optional[Tuple[Tensor, Tensor]] = None, differentiable: bool = False
                 ) -> Tuple[Tuple[Tensor, Tensor], Tuple[Tensor, Tensor]]:
+        """``differentiable=True``: the same values through ``hard_lstm_train``, so a loss reaches the input, ``hx`` and every
+        ``weight_*`` / ``bias_*``.  The default path is untouched."""
+        if differentiable:
+            from myrtlespeech_amd.model.rnn_autograd import hard_lstm_train
+            inp, lengths = x
+            out, hid = hard_lstm_train(self, inp.transpose(0, 1) if self.batch_first else inp, hx)
+            return (out.transpose(0, 1) if self.batch_first else out, lengths), hid
         _lib.require_gpu()
         inp, lengths = x
         data = _lib.f32c(inp.transpose(0, 1) if self.batch_first else inp)  # time-major [T, N, In]
