@@ -1294,6 +1294,44 @@ int ms_dropout_forward(const float* x, float* out, int64_t n, uint64_t thr, floa
 int ms_clamp_dropout_backward(const float* dy, const float* y, float* dx, int64_t n, float lo, float hi, uint64_t thr,
                               float scale, uint64_t seed, uint64_t offset, void* stream);
 
+/* ---- post_process/edit_distance.py, wer.py (DeviceWordErrorRate) ---------- */
+
+/* Batched edit distance with operation counts: what the reference's ReportCTCDecoder (run/run.py:50-109) computes on the host
+ * with post_process/utils.py's levenshtein, per utterance, on the device.  tests/edit_distance_ref.py restates this comment.
+ *
+ * Rows: hyp [n, hyp_stride] and ref [n, ref_stride] int32 labels, of which row u holds hyp_lens[u] / ref_lens[u] (clamped to
+ * [0, stride]); what lies past a row's length is never read.  A length of 0 is legal anywhere.
+ * Units.  mode = MS_EDIT_TOKENS: a row's units are its labels, as they are (separator and n_symbols are ignored).
+ *   mode = MS_EDIT_WORDS: first the labels outside [0, n_symbols) are dropped (Alphabet.get_symbols skips an index without a
+ *   symbol; the CTC blank is one); the rest is cut at every label equal to `separator`; empty words are dropped (WordSegmentor).
+ *   Two words are equal iff their label sequences are equal -- a hash only pre-filters.  separator = -1 (any value no kept
+ *   label takes): no separator, the row is one word, or none if nothing was kept.
+ * Distance and counts.  For hypothesis units a[0..m) and reference units b[0..n): D[i][0] = i insertions, D[0][j] = j deletions;
+ *   cell (i, j) takes the cheapest of, in this order, (1) (i-1, j-1) + (a[i-1] != b[j-1]): a match or a substitution,
+ *   (2) (i, j-1) + 1: a deletion (a reference unit the hypothesis lacks), (3) (i-1, j) + 1: an insertion; on equal cost the
+ *   first in that order wins.  The counts (S, D, I) of the chosen predecessor travel with the cost and the cell adds its own
+ *   operation.  out [n, 6] int32 = distance, S, D, I, m, n per utterance; distance is the reference's levenshtein(a, b);
+ *   S + D + I == distance and m - I == n - D by construction.
+ * totals: NULL, or int64 [6] (8-byte aligned) to which the six columns of this call are ADDED with integer atomics (any order
+ *   gives the same bits); the caller zeroes it, e.g. once per epoch.
+ * Launches on `stream`, no host read-back, no allocation: in word mode one workgroup per utterance turns both rows into unit
+ * ids (the index of the first equal word among the utterance's hypothesis and reference words) in the workspace; then the
+ * recurrence over anti-diagonals, a wave per utterance with the cells in registers when either side holds at most 63 units
+ * by its row width (stride in token mode, (stride + 1) / 2 words), else a workgroup per utterance with three rolling
+ * anti-diagonals in LDS.  LDS is sized by the strides, so a caller with short rows passes narrow matrices.
+ * Supported: 4096 units a side by the row widths -- hyp_stride, ref_stride <= MS_EDIT_MAX_LEN in token mode and
+ * <= 2 MS_EDIT_MAX_LEN - 1 in word mode (4096 one-letter words and their separators) -- beyond that MS_ERR_UNSUPPORTED and
+ * nothing is launched; a workspace below ms_edit_distance_workspace_bytes(n, hyp_stride, ref_stride)
+ * (host arithmetic; 0 for n <= 0) is MS_ERR_WORKSPACE; n = 0 is MS_OK with no launch.  Out of scope: the back-trace (which
+ * unit was substituted for which), weighted costs. */
+#define MS_EDIT_TOKENS 0
+#define MS_EDIT_WORDS 1
+#define MS_EDIT_MAX_LEN 4096
+size_t ms_edit_distance_workspace_bytes(int n, int max_hyp, int max_ref);
+int ms_edit_distance(const int32_t* hyp, int hyp_stride, const int32_t* hyp_lens, const int32_t* ref, int ref_stride,
+                     const int32_t* ref_lens, int n, int mode, int separator, int n_symbols, int32_t* out, int64_t* totals,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

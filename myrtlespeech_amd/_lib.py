@@ -164,6 +164,8 @@ SIGNATURES = {
     "ms_adam_step": (c_int, [_P, _P, _P, _P, _P, _P, c_int] + [c_float] * 6 + [_P, c_float, c_int, _P]),
     "ms_dropout_forward": (c_int, [_P, _P, c_int64, c_uint64, c_float, c_uint64, c_uint64, _P]),
     "ms_clamp_dropout_backward": (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_uint64, c_float, c_uint64, c_uint64, _P]),
+    "ms_edit_distance_workspace_bytes": (c_size_t, [c_int] * 3),
+    "ms_edit_distance": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -59,5 +59,22 @@ class CTCGreedyDecoder(torch.nn.Module):
         done.record()
         return PendingTranscripts(host, done, batch, keep=(packed, out_idx, out_len, xd, lens_dev))
 
+    def launch_device(self, x: torch.Tensor, lengths: torch.Tensor):
+        """The same decode left where it was made: ``(labels [N, T] int32, label_lens [N] int32)`` on the device, row ``n``
+        holding ``label_lens[n]`` labels.  No copy, no event, no wait: for consumers that stay on the device
+        (``wer.DeviceWordErrorRate``, ``post_process.edit_distance``)."""
+        seq_len, batch, symbols = check_decoder_args(x, lengths)
+        _lib.require_gpu()
+        out_idx = torch.empty((batch, seq_len), dtype=torch.int32, device="cuda")
+        if seq_len == 0 or batch == 0:
+            return out_idx, torch.zeros(batch, dtype=torch.int32, device="cuda")
+        out_len = torch.empty(batch, dtype=torch.int32, device="cuda")
+        xd = _lib.f32c(x)
+        lens_dev = _lib.lens_i32(lengths)
+        _lib.check(_lib.load().ms_ctc_greedy_decode(_lib.ptr(xd), _lib.ptr(lens_dev), _lib.ptr(out_idx),
+                                                    _lib.ptr(out_len), seq_len, batch, symbols, self.blank_index,
+                                                    _lib.stream_ptr()), "ms_ctc_greedy_decode")
+        return out_idx, out_len
+
     def extra_repr(self) -> str:
         return f"blank_index={self.blank_index}"

@@ -1,7 +1,12 @@
 """Decode -> transcripts -> word error rate: the arithmetic of the reference's
-``ReportCTCDecoder`` callback (run/run.py:29-109) without the callback plumbing."""
+``ReportCTCDecoder`` callback (run/run.py:29-109) without the callback plumbing (``run.callbacks.ReportCTCDecoder`` has it),
+on the host (``WordErrorRate``) and on the device (``DeviceWordErrorRate``)."""
 from typing import Iterable, List, Sequence, Tuple
 
+import torch
+
+from myrtlespeech_amd import _lib
+from myrtlespeech_amd.post_process.edit_distance import EditCounts, edit_distance
 from myrtlespeech_amd.post_process.utils import levenshtein
 
 
@@ -50,3 +55,58 @@ class WordErrorRate:
 
     def value(self) -> float:
         return float(sum(self.distances)) / sum(self.lengths) * 100
+
+
+class DeviceWordErrorRate:
+    """``WordErrorRate`` with the sums kept on the device: ``update`` launches ``ms_edit_distance`` on the batch and returns
+    without waiting, ``value()`` reads 48 bytes back once.  ``unit="word"`` counts the words ``WordSegmentor`` makes of
+    ``alphabet.get_symbols``; ``unit="token"`` counts labels.
+
+    The device compares words as label sequences, the host as joined strings.  The two agree iff joining is injective and
+    cutting happens at a label, so the constructor raises ``ValueError`` for a symbol that is not a single character, a segmentor
+    other than ``WordSegmentor`` and a separator that is not one character.  A one-character separator outside the alphabet
+    never occurs in ``get_symbols``' output: no separator (-1).  No transcripts are kept here; ``ReportCTCDecoder`` keeps them."""
+
+    def __init__(self, alphabet, word_segmentor, unit: str = "word"):
+        if unit not in ("word", "token"):
+            raise ValueError(f"unit={unit!r} must be 'word' or 'token'")
+        self.alphabet, self.word_segmentor, self.unit = alphabet, word_segmentor, unit
+        self.separator_index = None
+        if unit == "word":
+            multi = [s for s in alphabet.symbols if not isinstance(s, str) or len(s) != 1]
+            if multi:
+                raise ValueError(f"symbols {multi[:3]} are not single characters: equal words need not have equal labels")
+            if type(word_segmentor) is not WordSegmentor:
+                raise ValueError(f"{type(word_segmentor).__name__} is not wer.WordSegmentor: the device cuts words as it does")
+            separator = word_segmentor.separator
+            if not isinstance(separator, str) or len(separator) != 1:
+                raise ValueError(f"separator {separator!r} is not one character")
+            index = alphabet.get_index(separator)
+            self.separator_index = -1 if index is None else index
+        self._totals = None
+
+    def reset(self) -> None:
+        if self._totals is not None:
+            self._totals.zero_()
+
+    def update(self, hypotheses, targets, target_lens):
+        """``hypotheses``: ``CTCGreedyDecoder.launch_device``'s ``(labels, label_lens)`` pair, or a list of label lists.
+        Returns the batch's ``[N, 6]`` device tensor (``post_process.EditCounts`` rows)."""
+        if isinstance(hypotheses, tuple) and len(hypotheses) == 2 and isinstance(hypotheses[0], torch.Tensor) \
+                and hypotheses[0].dim() == 2:
+            hyp, hyp_lens = hypotheses
+        else:
+            hyp, hyp_lens = list(hypotheses), None
+        if self._totals is None:
+            _lib.require_gpu()
+            self._totals = torch.zeros(6, dtype=torch.int64, device="cuda")
+        return edit_distance(hyp, hyp_lens, targets, target_lens, separator_index=self.separator_index,
+                             n_symbols=len(self.alphabet) if self.unit == "word" else None, totals=self._totals)
+
+    def counts(self):
+        """The six sums so far (one read-back)."""
+        return EditCounts(*(self._totals.cpu().tolist() if self._totals is not None else [0] * 6))
+
+    def value(self) -> float:
+        c = self.counts()
+        return float(c.distance) / c.ref_units * 100
