@@ -38,8 +38,12 @@ def _n_words(prefix, sep):
 def search(x, length, blank_index: int, beam_width: int, prune_threshold: float = 0.001,
            language_model: Optional[Callable[[Tuple[int, ...]], float]] = None, lm_weight: Optional[float] = None,
            separator_index: Optional[int] = None, word_weight: float = 1.0, range_safe: bool = False,
-           dtype=np.float32) -> Search:
-    """One utterance: ``x [T, V]`` float32 posteriors, the first ``length`` rows."""
+           dtype=np.float32, hook: Optional[Callable] = None) -> Search:
+    """One utterance: ``x [T, V]`` float32 posteriors, the first ``length`` rows.
+
+    ``hook(t, scores, keys, pnb_only, order)`` is called once per frame, behind the sort: the sort scores and prefixes of
+    ``A_next`` in insertion order, how many of them exist in ``Pnb[t]`` only, and the stable descending order.  It may return
+    another order (the tie-break experiments of tests/test_beam_ties_cpu.py); None leaves the search as it is."""
     D = dtype
     ctc = np.asarray(x, dtype=F32)
     V = ctc.shape[1]
@@ -91,6 +95,9 @@ def search(x, length, blank_index: int, beam_width: int, prune_threshold: float 
         else:
             keyed = [(D(a_next[k] * D(F32((1 + _n_words(k, separator_index)) ** word_weight))), k) for k in a_next]
         order = sorted(range(len(keyed)), key=lambda j: -float(keyed[j][0]))      # stable, descending
+        if hook is not None:
+            pnb_only = sum(1 for k in a_next if k not in pb)
+            order = hook(t, [s for s, _ in keyed], [k for _, k in keyed], pnb_only, order) or order
         a_prev = [keyed[j][1] for j in order][:beam_width]
         if range_safe and a_prev:
             s0 = D(pb.get(a_prev[0], zero) + pnb.get(a_prev[0], zero))

@@ -1294,3 +1294,31 @@ def gen_streaming_n64_trained_scale(gains=TRAINED_GAINS, save_it=True):
 
 if __name__ == "__main__" and "stream64trained" in sys.argv[1:]:
     gen_streaming_n64_trained_scale(save_it="probe" not in sys.argv[1:])
+
+
+# ----------------------------------------------------------------------------- beam search on exact ties
+def gen_beam_ties():
+    """The reference CTCBeamDecoder on the tie clips of tests/beam_tie_cases.py -- every case that is not range-safe, with its
+    separator / word weight and (an entry of its own) without.  Inputs are regenerated from their seeds in the tests; a
+    strided probe and the absolute sum of each pin them."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import beam_tie_cases as C
+    arrays, entries = {}, []
+    for name in C.CASES:
+        c = C.case(name)
+        if c.range_safe:
+            continue
+        x, lens = torch.from_numpy(c.x.copy()), torch.tensor(c.lens, dtype=torch.int64)
+        arrays[f"{name}/x_probe"] = c.x[::5, :, ::7].copy()
+        arrays[f"{name}/x_abs_sum"] = np.array(float(np.abs(c.x.astype(np.float64)).sum()))
+        for tag, kw in (("plain", dict()), ("words", dict(separator_index=c.sep, word_weight=c.word_weight))):
+            if tag == "words" and c.sep is None:
+                continue
+            out = CTCBeamDecoder(blank_index=c.blank, beam_width=c.width, prune_threshold=c.prune, **kw)(x, lens)
+            arrays[f"{name}/{tag}_flat"], arrays[f"{name}/{tag}_lens"] = ragged(out)
+            entries.append(dict(case=name, tag=tag))
+    save("beam_ties", dict(entries=entries), arrays)
+
+
+if __name__ == "__main__" and "beamties" in sys.argv[1:]:
+    gen_beam_ties()

@@ -339,6 +339,26 @@ def test_wer_fixture_pins_levenshtein_alphabet_and_wer():
     assert wer.value() == c["wer"]
 
 
+def test_beam_ties():
+    """The numpy beam search against the reference on the clips of tests/beam_tie_cases.py, where bit-equal scores leave the
+    beam to the insertion order of the reference's Counters: every entry of the fixture (each case that is not range-safe,
+    with and without its separator / word weight), the inputs regenerated from their seeds and held to the stored probe."""
+    import beam_tie_cases as C
+    g = Golden("beam_ties")
+    entries = g.cfg["entries"]
+    assert {e["case"] for e in entries} == {n for n in C.CASES if not C.case(n).range_safe}
+    for e in entries:
+        c = C.case(e["case"])
+        np.testing.assert_array_equal(c.x[::5, :, ::7], g[f"{c.name}/x_probe"])
+        assert float(np.abs(c.x.astype(np.float64)).sum()) == float(g[f"{c.name}/x_abs_sum"])
+        words = e["tag"] == "words"
+        assert not words or c.sep is not None
+        want = unragged(g[f"{c.name}/{e['tag']}_flat"], g[f"{c.name}/{e['tag']}_lens"])
+        got = O.ctc_beam_decode(c.x, np.asarray(c.lens), c.blank, c.width, c.prune,
+                                separator_index=c.sep if words else None, word_weight=c.word_weight if words else 1.0)
+        assert got == want, e
+
+
 def test_beam_oracle_config_size_vs_reference():
     """The numpy beam search against the reference at T = 501, V = 29, beam 8 (one of the four utterances; the pure-Python
     oracle takes ~1.5 s per utterance like the reference)."""
